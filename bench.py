@@ -10,8 +10,16 @@ At N GPUs the tables are row-sharded (owner = key % N) and every step sends
 the ids to their owners, resolves them there and brings the rows back: over
 xGMI peer writes (XgmiShardedLookup), or the RCCL all-to-all engine
 (ShardedLookup) when IPC mapping is unavailable; per-GPU work is fixed
-(weak scaling).  The JSON line carries the roofline of the dominant kernel
-and, for the north_star's row-gather target, of the pre-resolved gather.
+(weak scaling).
+
+A plain run sets the tables up, warms up, times the steps, writes the last
+timed step's output if --dump-outputs DIR is given, and prints the result
+line.  With --full it goes on to everything else the benchmark measures and
+checks (native C-ABI engine, parity at the headline size, training steps,
+the DLRM and DIN model steps, the other configurations' legs, the CPU
+baseline); the JSON line then also carries the roofline of the dominant
+kernel and, for the north_star's row-gather target, of the pre-resolved
+gather.  Without --full those entries are null.
 
 Timing: W untimed warmup steps, then exactly K steps bracketed by a barrier
 and torch.cuda.synchronize(); max over ranks; rank 0 prints one JSON line.
@@ -46,6 +54,14 @@ def parse():
     p.add_argument("--batch", type=int, default=65536, help="per-GPU batch (B_local)")
     p.add_argument("--zipf", type=float, default=0.0, help="0 = uniform keys")
     p.add_argument("--no-graph", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline: the native engine, parity, training-step, model, "
+                        "per-kernel roofline, CPU baseline and other-configuration legs (the "
+                        "options below them apply only with --full); a plain run sets up, warms "
+                        "up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's output (float32 .npy, a fixed seeded "
+                        "sample of its rows when larger than 48 MB) into DIR")
     p.add_argument("--cpu-seconds", type=float, default=18.0)
     p.add_argument("--cpu-rows", type=int, default=12_500_000)
     p.add_argument("--check-rows", type=int, default=8192,
@@ -232,6 +248,29 @@ def check_rows(out, ids, T, D, n_sample, seed):
                                  "(first key %d)" % (tt, bad.shape[0], sel.sum(),
                                                      keys[sel][bad[0]]))
     return int(n_sample)
+
+
+DUMP_MAX_BYTES = 48 << 20      # of float32, over all ranks
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: each named output tensor as DIR/<name>.npy, float32
+    (DIR/<name>.rank<r>.npy at N > 1).  An output above DUMP_MAX_BYTES is
+    written as a fixed sample of its rows (drawn without replacement from a
+    generator seeded with the row count alone, in ascending order), so two
+    builds given the same arguments write the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(t.shape[0], -1)
+        keep = max(1, DUMP_MAX_BYTES // world // (4 * t.shape[1]))
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(t.shape[0]).choice(t.shape[0], keep,
+                                                                    replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+        a = t.float().cpu().numpy()
+        path = os.path.join(dirname, name + (".rank%d" % rank if world > 1 else "") + ".npy")
+        np.save(path, a)
+        log("dumped %s %s to %s" % (name, list(a.shape), path))
 
 
 def _onehot_kernel_ms(feat_sets, iters, out_dtype=None):
@@ -1289,6 +1328,7 @@ def main():
                 for k in range(NBATCH):
                     out = step(k)
             log("graphs captured")
+            graph_out = out     # a replay leaves its last step's output here
             graph_all.replay()
             torch.cuda.synchronize()
             log("graph replay ok")
@@ -1296,17 +1336,23 @@ def main():
         debug = os.environ.get("DR_BENCH_DEBUG") == "1"
 
         def run_steps(i0, n):
-            i = i0
+            """Steps i0 .. i0 + n - 1; returns the output of the last one."""
+            i, last = i0, None
             while i < i0 + n:
                 if graph_all is not None and i % NBATCH == 0 and i + NBATCH <= i0 + n:
                     graph_all.replay()
+                    last = graph_out
                     i += NBATCH
                     continue
-                step(i % NBATCH)
+                if i == i0 + n - 1:
+                    last = step(i % NBATCH)
+                else:
+                    step(i % NBATCH)
                 if debug:
                     torch.cuda.synchronize()
                     log("step %d: done" % i)
                 i += 1
+            return last
 
         # N > 1 peer-write engine: HIP events between its phases during the
         # timed steps (route / barrier / serve / barrier; phase_summary)
@@ -1321,11 +1367,15 @@ def main():
             if phase_engine is not None:
                 phase_engine.phase_timing(True)
             t0 = time.perf_counter()
-            run_steps(0, args.steps)
+            last = run_steps(0, args.steps)
             if dist is not None:
                 dist.barrier()
             torch.cuda.synchronize()
-            return time.perf_counter() - t0
+            el = time.perf_counter() - t0
+            if args.dump_outputs and last is not None:
+                # now: a sharded engine's next forward reuses this buffer
+                dump_outputs(args.dump_outputs, {"embedding_output": last}, rank, world)
+            return el
 
         el = timed()
         log("timed %d steps in %.3fs" % (args.steps, el))
@@ -1359,6 +1409,67 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device="cpu" if staged else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    lookups = T * B * args.steps * world
+    value = lookups / el
+    ms = el / args.steps * 1e3
+    native = correctness = train = dlrm = din = roof = roof_gather = cpu = None
+    deepfm = criteo = dcn = hybrid = None
+
+    def finish():
+        """Rank 0 prints the result line (the legs that did not run: null)."""
+        if rank == 0:
+            with open(os.path.join(ROOT, "BASELINE.json")) as f:
+                metric = json.load(f)["metric"]
+            line = {
+                "metric": metric,
+                "value": round(value, 1),
+                "unit": "lookups/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(ms, 4),
+                "higher_is_better": True,
+                "scaling": "weak",
+                "vs_baseline": None,
+                "dtype": "fp32",
+                "full": args.full,
+                "data": "synthetic (uniform keys%s, hash-derived table rows)" % (
+                    "" if args.zipf <= 0 else ", zipf %.2f" % args.zipf),
+                "config": {"workload": "DLRM Criteo-TB shape: %d EV tables x %d rows/GPU x %d fp32, "
+                                       "B_local=%d, hotness 1, embedding_lookup_sparse(sum) forward "
+                                       "(EV insert-on-miss resolve of every id -> fused gather+pool; "
+                                       "forward-only filter-free one-hot needs no Unique)%s"
+                                       % (T, R, D, B, "; %s exchange: ids to owners (key %% N), "
+                                          "owner resolve, rows back" % engine_kind
+                                          if world > 1 else ""),
+                           "global_batch": B * world, "tables": T, "rows_per_gpu": R, "dim": D,
+                           "engine": engine_kind, "engine_check": engine_check,
+                           "parallelism": "row-sharded tables x%d, data-parallel batch" % world},
+                "forward_samples_per_s": round(value / T, 1),
+                "train_step": train,
+                "dlrm_train_step": dlrm,
+                "din_config": din,
+                "deepfm_config": deepfm,
+                "criteo_tb_cardinalities": criteo,
+                "criteo_tb_hybrid": hybrid,
+                "exchange_phases": phases,
+                "native_engine": native,
+                "dcn_bf16_config": dcn,
+                "correctness": correctness,
+                "roofline": roof,
+                "roofline_row_gather": roof_gather,
+                "cpu_baseline": cpu,
+            }
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run ends here: the headline figure needs nothing below
+        dr.status_check(dev)
+        finish()
+        return
     # the library's own sharded C entries (dr_sharded_forward over a dr_comm:
     # RCCL, ncclUniqueId through torch.distributed; N = 1 too, where every
     # all-to-all is the self block inside an RCCL group) beside the headline
@@ -1370,9 +1481,6 @@ def main():
         except Exception as e:  # noqa: BLE001 -- an extra leg must not cost the headline line
             log("native RCCL leg failed: %r" % (e,))
             native = {"error": str(e)[:300]}
-    lookups = T * B * args.steps * world
-    value = lookups / el
-    ms = el / args.steps * 1e3
     dr.status_check(dev)
 
     # ---- parity at the headline size, outside the timed region: sampled
@@ -1752,52 +1860,7 @@ def main():
             hybrid = criteo_hybrid_leg(args, dev, log, world, rank, dist, staged)
             _free_hbm()
 
-    if rank == 0:
-        with open(os.path.join(ROOT, "BASELINE.json")) as f:
-            metric = json.load(f)["metric"]
-        line = {
-            "metric": metric,
-            "value": round(value, 1),
-            "unit": "lookups/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic (uniform keys%s, hash-derived table rows)" % (
-                "" if args.zipf <= 0 else ", zipf %.2f" % args.zipf),
-            "config": {"workload": "DLRM Criteo-TB shape: %d EV tables x %d rows/GPU x %d fp32, "
-                                   "B_local=%d, hotness 1, embedding_lookup_sparse(sum) forward "
-                                   "(EV insert-on-miss resolve of every id -> fused gather+pool; "
-                                   "forward-only filter-free one-hot needs no Unique)%s"
-                                   % (T, R, D, B, "; %s exchange: ids to owners (key %% N), "
-                                      "owner resolve, rows back" % engine_kind
-                                      if world > 1 else ""),
-                       "global_batch": B * world, "tables": T, "rows_per_gpu": R, "dim": D,
-                       "engine": engine_kind, "engine_check": engine_check,
-                       "parallelism": "row-sharded tables x%d, data-parallel batch" % world},
-            "forward_samples_per_s": round(value / T, 1),
-            "train_step": train,
-            "dlrm_train_step": dlrm,
-            "din_config": din,
-            "deepfm_config": deepfm,
-            "criteo_tb_cardinalities": criteo,
-            "criteo_tb_hybrid": hybrid,
-            "exchange_phases": phases,
-            "native_engine": native,
-            "dcn_bf16_config": dcn,
-            "correctness": correctness,
-            "roofline": roof,
-            "roofline_row_gather": roof_gather,
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(line), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

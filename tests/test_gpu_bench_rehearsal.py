@@ -30,7 +30,7 @@ def test_bench_two_rank_rehearsal(engine):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1",
            "--master-port", {"xgmi": "29531", "xgmi-dedup": "29533", "a2a": "29532"}[engine],
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "2",
            "--rows", "200000", "--batch", "8192", "--tables", "8", "--cpu-seconds", "0",
            "--check-rows", "4096", "--engine", engine.split("-")[0], "--train-steps", "3",
            "--hybrid-cap", "1000000", "--model-steps", "3", "--din-steps", "3",

@@ -64,7 +64,7 @@ def main():
         "kernel": KERNEL,
         "source": os.environ.get("PMC_SOURCE") or
                   "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, "
-                  "bench.py --no-graph --steps 2 --kernel-iters 3; median over dispatches",
+                  "bench.py --full --no-graph --steps 2 --kernel-iters 3; median over dispatches",
         "fetch_size_kib_raw_median": statistics.median(fetch),
         "write_size_kib_raw_median": statistics.median(write),
         "dispatches": [len(fetch), len(write)],
