@@ -2627,6 +2627,294 @@ static int lookup_onehot(dr_ev* const* evs, int T, const int64_t* keys, int64_t 
   return DR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Read-only lookups (EmbeddingVar::Lookup, the reference's inference mode):
+// hit -> the stored row, miss -> a default, nothing created.  A key is served
+// its row iff (1) it is in the map with a published, live row, (2) this
+// column's first-touch bit is set -- both are what the read-only probes above
+// (ev_probe_row, line_probe_resolve) already decide -- and (3) for a Counter
+// EV freq[row] >= filter_freq.  A Bloom EV's counters are not consulted:
+// admitted keys are the ones in the map.  Plain loads only: no CAS, no
+// counter, no version stamp, no first-touch bit, and on the host no
+// reserve() / mirror, so slots, top, freq, version, the pools and the
+// capacity accounting are what they were.
+// ---------------------------------------------------------------------------
+struct RoDesc {
+  const Slot* slots;
+  int64_t cap;
+  const float* pool;
+  uint64_t colbit;
+  const float* dflt;    // the column's default row
+  const int64_t* freq;  // Counter EVs only (else nullptr: no admission test)
+  int64_t filter_freq;
+};
+
+static RoDesc make_ro_desc(const dr_ev* ev) {
+  const EvShared* s = ev->sh;
+  RoDesc d;
+  d.slots = s->slots;
+  d.cap = s->cap;
+  d.pool = s->pools[ev->col];
+  d.colbit = 1ull << (48 + ev->col);
+  d.dflt = s->defaults[ev->col];
+  const bool counter = s->filter_freq > 0 && s->k_hash == 0 && s->freq;
+  d.freq = counter ? s->freq : nullptr;
+  d.filter_freq = counter ? s->filter_freq : 0;
+  return d;
+}
+
+struct RoGroup {
+  RoDesc d[DR_MAX_GROUP];
+  int64_t koff[DR_MAX_GROUP + 1];
+  const int64_t* n_dev[DR_MAX_GROUP];
+};
+static_assert(sizeof(RoGroup) + 64 <= 4096, "find kernel arguments exceed 4 KiB");
+
+// Row of `key` when it is to be served (rules 1-3), else -1.
+__device__ __forceinline__ int64_t ro_row(const RoDesc& e, uint64_t key) {
+  LkDesc lk;
+  lk.slots = e.slots;
+  lk.cap = e.cap;
+  lk.pool = e.pool;
+  lk.colbit = e.colbit;
+  int64_t row = ev_probe_row(lk, key);
+  if (row >= 0 && e.freq && gld(e.freq + row) < e.filter_freq) row = -1;
+  return row;
+}
+
+// Grouped read-only resolve, lane per key (the grouping of ev_resolve_kernel):
+// rows_out[i] = row, or -(li + 1) when the default is to be served.
+__global__ void ev_find_kernel(RoGroup g, int T, const int64_t* __restrict__ keys,
+                               int64_t* __restrict__ rows_out) {
+  __shared__ RoDesc sd[DR_MAX_GROUP];
+  if (threadIdx.x < T) sd[threadIdx.x] = g.d[threadIdx.x];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.koff[T]) return;
+  const int t = table_of(g.koff, T, i, (int64_t)blockIdx.x * blockDim.x);
+  const int64_t li = i - g.koff[t];
+  if (g.n_dev[t] && li >= *g.n_dev[t]) return;
+  const int64_t row = ro_row(sd[t], (uint64_t)keys[i]);
+  rows_out[i] = row >= 0 ? row : -(li + 1);
+}
+
+// Read-only gather, G lanes per key: out[i] = the key's row, defaults[i]
+// (nullable) or the column's default row.  The G lanes probe together (the
+// same addresses: one request), so there is no row-index array in between.
+// `words`: float words per row; vec: rows and bases 16-B aligned.
+template <int G>
+__global__ __launch_bounds__(256) void ev_gather_ro_kernel(
+    RoDesc e, int64_t words, int vec, const int64_t* __restrict__ keys, int64_t n,
+    const float* __restrict__ defaults, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  if (i >= n) return;
+  const int lg = threadIdx.x % G;
+  const int64_t row = ro_row(e, (uint64_t)keys[i]);
+  const float* src = row >= 0 ? e.pool + row * words : (defaults ? defaults + i * words : e.dflt);
+  float* dst = out + i * words;
+  if (vec) {
+    for (int64_t c = lg; c < words / 4; c += G)
+      reinterpret_cast<float4*>(dst)[c] = gld(reinterpret_cast<const float4*>(src) + c);
+  } else {
+    for (int64_t c = lg; c < words; c += G) dst[c] = gld(src + c);
+  }
+}
+
+struct RoLookupArgs {
+  RoDesc d[DR_MAX_GROUP];
+  const int64_t* keys;  // id of (bag b, table t) = keys[b * ksb + t * kst]
+  int64_t ksb, kst;
+  float* out;
+  int64_t out_stride;
+  int64_t* rows;  // row served per id (-1: default), or nullptr
+  int tmaj;       // visit slots table by table (s = t * B + b)
+  int rrec;       // rows record-major: rows[b * T + t]
+};
+static_assert(sizeof(RoLookupArgs) + 64 <= 4096, "lookup kernel arguments exceed 4 KiB");
+
+// Slot s -> (bag, table) in the visiting order (T * B < 2^31: host check).
+__device__ __forceinline__ void ro_slot_bt(int64_t s, int T, int64_t B, int tmaj, int64_t* b,
+                                           int* t) {
+  const uint32_t dv = tmaj ? (uint32_t)B : (uint32_t)T;
+  const uint32_t q = (uint32_t)s / dv, r = (uint32_t)s - q * dv;
+  *b = tmaj ? (int64_t)r : (int64_t)q;
+  *t = tmaj ? (int)q : (int)r;
+}
+
+// Fused one-hot read-only lookup: the 8-lanes-per-key home-line probe of
+// ev_lookup_line_kernel, then the row copy -- and nothing else.  A key that
+// is not served points its row address at the table's default row, so there
+// is no miss list and no second kernel.  Every load and store is
+// unconditional without a junk sink: a lane past the row's last chunk holds a
+// copy of that chunk (the clamped load) and stores it to the same place, and
+// the slots past T * B of the last wave are clamped to slot T * B - 1, whose
+// key, row and output address they repeat (same bytes to the same address).
+template <int VEC, int G, int ORDER, bool WIDEN = false>
+__global__ __launch_bounds__(256) void ev_lookup_ro_kernel(RoLookupArgs a, int T, int64_t B,
+                                                           int dim) {
+  constexpr int NB = G / 8;
+  static_assert(NB * 8 == G, "8 lanes per key, 8 keys per wave");
+  __shared__ RoDesc sd[DR_MAX_GROUP];
+  const int64_t slots = (int64_t)T * B;
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t ws0 = ((int64_t)blockIdx.x * 4 + threadIdx.x / 64) * 8;  // wave's first slot
+  const int64_t s = ws0 + (lane >> 3);
+  const bool valid = s < slots;
+  int64_t b;
+  int t;
+  ro_slot_bt(valid ? s : slots - 1, T, B, a.tmaj, &b, &t);
+  // the id's round trip overlaps the descriptor staging (ids read once)
+  const uint64_t key =
+      (uint64_t)__builtin_nontemporal_load(gp(a.keys + b * a.ksb + (int64_t)t * a.kst));
+  if (threadIdx.x < T) sd[threadIdx.x] = a.d[threadIdx.x];
+  __syncthreads();
+  if (ws0 >= slots) return;  // whole waves
+  const Slot* tsl = sd[t].slots;
+  const int64_t tcap = sd[t].cap;
+  int64_t row = line_probe_resolve(tsl, tcap, sd[t].colbit, key,
+                                   line_probe_issue(tsl, tcap, key, lane & 7), lane);
+  // Counter admission: uniform per table, filter-free tables skip it
+  const int64_t* fq = sd[t].freq;
+  if (fq && row >= 0 && gld(fq + row) < sd[t].filter_freq) row = -1;
+  if ((lane & 7) == 0 && valid && a.rows)
+    a.rows[a.rrec ? b * T + t : (int64_t)t * B + b] = row;
+  const int64_t rstride = WIDEN ? dim / 2 : dim;
+  const uint64_t mine =
+      (uint64_t)(uintptr_t)(row >= 0 ? sd[t].pool + row * rstride : sd[t].dflt);
+  const int lg = lane % G, base = lane - lg;
+  const int dv = dim / VEC;
+  const float* p[NB];
+#pragma unroll
+  for (int q = 0; q < NB; ++q) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)mine, base + 8 * q, 64);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(mine >> 32), base + 8 * q, 64);
+    p[q] = reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo));
+  }
+  Row<VEC, G, 1> x[NB];
+#pragma unroll
+  for (int q = 0; q < NB; ++q) load_row_copy_u<VEC, G, 1, WIDEN>(x[q], p[q], lg, dv);
+  const int col = lg < dv ? lg : dv - 1;
+#pragma unroll
+  for (int q = 0; q < NB; ++q) {
+    int64_t sq = ws0 + (base / G) * NB + q;
+    sq = sq < slots ? sq : slots - 1;
+    int64_t bq;
+    int tq;
+    ro_slot_bt(sq, T, B, a.tmaj, &bq, &tq);
+    if (ORDER == DR_ORDER_SEQ)  // fused op: out = 0 + e (-0.0 -> +0.0)
+      x[q].v[0] = vadd(vzero<typename VecT<VEC>::T>(), x[q].v[0]);
+    float* dst = a.out + bq * a.out_stride + (int64_t)tq * dim + (int64_t)col * VEC;
+    nt_store(x[q].v[0], reinterpret_cast<typename VecT<VEC>::T*>(dst));
+  }
+}
+
+template <int G, int ORDER, bool WIDEN>
+static void launch_lookup_ro(const RoLookupArgs& a, int T, int64_t B, int dim, hipStream_t st) {
+  const int64_t waves = ceil_div((int64_t)T * B, 8);
+  timing_mark(DR_TIME_LOOKUP, st, true);
+  hipLaunchKernelGGL((ev_lookup_ro_kernel<4, G, ORDER, WIDEN>), dim3((unsigned)ceil_div(waves, 4)),
+                     dim3(256), 0, st, a, T, B, dim);
+  timing_mark(DR_TIME_LOOKUP, st, false);
+}
+
+static int find_grouped(dr_ev* const* evs, int T, const int64_t* keys, const int64_t* koff,
+                        const int64_t* const* n_dev, int64_t* rows_out, hipStream_t st) {
+  DR_REQUIRE(evs && koff && T >= 1 && T <= DR_MAX_GROUP, DR_INVALID_ARGUMENT, "bad argument");
+  for (int t = 0; t < T; ++t) {
+    DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
+    DR_REQUIRE(koff[t] >= 0 && koff[t + 1] >= koff[t], DR_INVALID_ARGUMENT,
+               "koff must be non-decreasing from >= 0");
+  }
+  const int64_t total = koff[T];
+  DR_REQUIRE(total == 0 || (keys && rows_out), DR_INVALID_ARGUMENT, "null keys / rows_out");
+  EvGuard guard_(evs, T);
+  if (total == 0) return DR_OK;
+  RoGroup g;
+  memset(&g, 0, sizeof(g));
+  for (int t = 0; t < T; ++t) {
+    g.d[t] = make_ro_desc(evs[t]);
+    g.koff[t] = koff[t];
+    g.n_dev[t] = n_dev ? n_dev[t] : nullptr;
+  }
+  g.koff[T] = total;
+  hipLaunchKernelGGL(ev_find_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, g, T,
+                     keys, rows_out);
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+static int lookup_onehot_readonly(dr_ev* const* evs, int T, const int64_t* keys, int64_t ksb,
+                                  int64_t kst, int64_t B, float* out, int64_t out_stride,
+                                  int order, int flags, int64_t* rows_out, hipStream_t st) {
+  DR_REQUIRE(evs && T >= 1 && T <= DR_MAX_GROUP && B >= 0 && out_stride >= 0, DR_INVALID_ARGUMENT,
+             "bad argument");
+  for (int t = 0; t < T; ++t) DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
+  DR_REQUIRE(ksb >= 0 && kst >= 0, DR_INVALID_ARGUMENT, "key strides must be >= 0");
+  DR_REQUIRE(order == DR_ORDER_ALI || order == DR_ORDER_SEQ, DR_INVALID_ARGUMENT, "bad order");
+  const int64_t n = (int64_t)T * B;
+  DR_REQUIRE(n < (1ll << 31), DR_INVALID_ARGUMENT, "T*B must be < 2^31");
+  DR_REQUIRE(n == 0 || (keys && out), DR_INVALID_ARGUMENT, "null keys / out");
+  DR_REQUIRE((flags & ~(DR_LOOKUP_OUT_BF16 | DR_LOOKUP_TABLE_ORDER | DR_LOOKUP_ROWS_RECORD)) == 0,
+             DR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+  EvGuard guard_(evs, T);
+  // value types as in lookup_onehot: bf16 rows widened into an fp32 output,
+  // or (DR_LOOKUP_OUT_BF16) copied bitwise as D / 2 float words
+  const bool bf16 = evs[0]->sh->bf16 && evs[0]->col == 0;
+  const bool out_bf16 = flags & DR_LOOKUP_OUT_BF16;
+  const bool widen = bf16 && !out_bf16;
+  DR_REQUIRE(!out_bf16 || bf16, DR_INVALID_ARGUMENT, "DR_LOOKUP_OUT_BF16 needs bf16 EVs");
+  DR_REQUIRE(!bf16 || order == DR_ORDER_ALI, DR_INVALID_ARGUMENT,
+             "bf16 EV lookups pool in the ALI order");
+  DR_REQUIRE(!out_bf16 || out_stride % 2 == 0, DR_INVALID_ARGUMENT,
+             "bf16 output stride must be even");
+  if (out_bf16) out_stride /= 2;  // float words from here on
+  const int64_t dim = bf16 && !widen ? col_words(evs[0]->sh, 0) : evs[0]->sh->dim;
+  DR_REQUIRE(dim % 4 == 0 && dim <= 256, DR_INVALID_ARGUMENT,
+             "fused one-hot lookup needs dim %% 4 == 0 (bf16: %% 8) and <= 256 words");
+  DR_REQUIRE(out_stride >= (int64_t)T * dim && (out_stride % 4) == 0 &&
+                 ((uintptr_t)out & 15) == 0,
+             DR_INVALID_ARGUMENT, "out must be 16-B aligned with stride >= T*dim (multiple of 4)");
+  if (n == 0) return DR_OK;
+  RoLookupArgs la;
+  memset(&la, 0, sizeof(la));
+  for (int t = 0; t < T; ++t) {
+    const EvShared* s = evs[t]->sh;
+    DR_REQUIRE(s->dim == evs[0]->sh->dim && (s->bf16 && evs[t]->col == 0) == bf16,
+               DR_INVALID_ARGUMENT, "tables must share dim and value type");
+    DR_REQUIRE(s->value_words == 1, DR_INVALID_ARGUMENT,
+               "table %d: pooled lookups are fp32 / bf16 (double EVs: dr_ev_gather_readonly)", t);
+    DR_REQUIRE(((uintptr_t)s->pools[evs[t]->col] & 15) == 0 &&
+                   ((uintptr_t)s->defaults[evs[t]->col] & 15) == 0,
+               DR_INVALID_ARGUMENT, "pool alignment");
+    la.d[t] = make_ro_desc(evs[t]);
+  }
+  la.keys = keys;
+  la.ksb = ksb;
+  la.kst = kst;
+  la.rows = rows_out;
+  la.out = out;
+  la.out_stride = out_stride;
+  la.tmaj = (flags & DR_LOOKUP_TABLE_ORDER) ? 1 : 0;
+  la.rrec = (flags & DR_LOOKUP_ROWS_RECORD) ? 1 : 0;
+  const int d4 = (int)(dim / 4);
+#define DR_RO(G)                                                              \
+  do {                                                                        \
+    if (widen)                                                                \
+      launch_lookup_ro<G, DR_ORDER_ALI, true>(la, T, B, (int)dim, st);        \
+    else if (order == DR_ORDER_ALI)                                           \
+      launch_lookup_ro<G, DR_ORDER_ALI, false>(la, T, B, (int)dim, st);       \
+    else                                                                      \
+      launch_lookup_ro<G, DR_ORDER_SEQ, false>(la, T, B, (int)dim, st);       \
+  } while (0)
+  if (d4 <= 8) DR_RO(8);
+  else if (d4 <= 16) DR_RO(16);
+  else if (d4 <= 32) DR_RO(32);
+  else DR_RO(64);
+#undef DR_RO
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
 }  // namespace dr
 
 // ===========================================================================
@@ -3016,6 +3304,45 @@ size_t dr_ev_gather_workspace_size(int64_t n) {
   c.take<int64_t>(n > 0 ? n : 1);
   c.take<char>(dr_ev_resolve_workspace_size(n));
   return c.used + 256;
+}
+
+// ---- read-only lookups (see RoDesc) ----------------------------------------
+int dr_ev_find_grouped(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                       const int64_t* koff_host, const int64_t* const* n_dev_per_table,
+                       int64_t* rows_out, void* stream) {
+  return dr::find_grouped(evs, num_tables, keys, koff_host, n_dev_per_table, rows_out,
+                          dr::S(stream));
+}
+
+// rows move as float words whatever the value type (double: 2 per value,
+// bf16: one per pair), as in dr_ev_gather
+int dr_ev_gather_readonly(dr_ev* ev, const int64_t* keys, int64_t n, const void* defaults,
+                          void* out, void* stream) {
+  using namespace dr;
+  DR_REQUIRE(ev && n >= 0, DR_INVALID_ARGUMENT, "bad argument");
+  DR_REQUIRE(n == 0 || (keys && out), DR_INVALID_ARGUMENT, "null keys / out");
+  EvGuard guard_(ev);
+  if (n == 0) return DR_OK;
+  const RoDesc e = make_ro_desc(ev);
+  const int64_t words = col_words(ev->sh, ev->col);
+  const int vec = words % 4 == 0 &&
+                  (((uintptr_t)e.pool | (uintptr_t)e.dflt | (uintptr_t)defaults | (uintptr_t)out) &
+                   15) == 0;
+  constexpr int G = 16;
+  hipLaunchKernelGGL(ev_gather_ro_kernel<G>, dim3((unsigned)ceil_div(n, 256 / G)), dim3(256), 0,
+                     S(stream), e, words, vec, keys, n, static_cast<const float*>(defaults),
+                     static_cast<float*>(out));
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+int dr_ev_lookup_onehot_readonly(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                                 int64_t key_stride_bag, int64_t key_stride_table,
+                                 int64_t batch, void* out, int64_t out_stride, int order,
+                                 int flags, int64_t* rows_out, void* stream) {
+  return dr::lookup_onehot_readonly(evs, num_tables, keys, key_stride_bag, key_stride_table,
+                                    batch, static_cast<float*>(out), out_stride, order, flags,
+                                    rows_out, dr::S(stream));
 }
 
 int dr_ev_insert(dr_ev* ev, const int64_t* keys, int64_t n, const float* values,

@@ -188,4 +188,88 @@ int dr_embedding_lookup_sparse(dr_ev* ev, const float* table, int64_t table_rows
   return DR_OK;
 }
 
+// The same composition over an EV read-only (evaluation / serving): prune /
+// fill, bag offsets, dr_ev_find_grouped of every id (no counts to merge, so
+// no Unique and no host read of its length), pooling with the EV's default
+// row for the ids that are not served.
+size_t dr_embedding_lookup_sparse_readonly_workspace_size(int64_t nnz, int64_t batch) {
+  return dr_embedding_lookup_sparse_workspace_size(nnz, batch);
+}
+
+int dr_embedding_lookup_sparse_readonly(dr_ev* ev, const float* table, int64_t table_rows,
+                                        int dim, const int64_t* sp_indices,
+                                        const int64_t* sp_values, const float* sp_weights,
+                                        int64_t nnz, int64_t batch, int combiner,
+                                        float max_norm, int safe, int64_t default_id, int prune,
+                                        float* out, int64_t out_stride, void* ws,
+                                        size_t ws_bytes, void* stream) {
+  using namespace dr;
+  (void)table_rows;
+  DR_REQUIRE(ev && !table, DR_INVALID_ARGUMENT, "the read-only lookup takes an ev (table NULL)");
+  EvGuardRef guard_(ev);
+  DR_REQUIRE(nnz >= 0 && batch >= 0 && dim > 0 && out && out_stride >= dim,
+             DR_INVALID_ARGUMENT, "bad shape");
+  DR_REQUIRE(nnz == 0 || (sp_indices && sp_values), DR_INVALID_ARGUMENT, "null sparse input");
+  DR_REQUIRE(combiner >= DR_COMBINER_SUM && combiner <= DR_COMBINER_SQRTN, DR_INVALID_ARGUMENT,
+             "combiner must be sum, mean or sqrtn");
+  DR_REQUIRE(nnz + batch < (1ll << 31), DR_INVALID_ARGUMENT, "nnz + batch must be < 2^31");
+  DR_REQUIRE(ws_bytes >= dr_embedding_lookup_sparse_readonly_workspace_size(nnz, batch),
+             DR_INVALID_ARGUMENT, "workspace too small");
+  DR_REQUIRE(dr_ev_dim(ev) == dim, DR_INVALID_ARGUMENT, "dim %d != the EV's %lld", dim,
+             (long long)dr_ev_dim(ev));
+  const int vb = dr_ev_value_bits(ev);
+  DR_REQUIRE(vb == 32 || (vb == 16 && dim % 8 == 0), DR_INVALID_ARGUMENT,
+             "embedding lookups pool float32 EVs, or bf16 EVs with dim %% 8 == 0");
+  if (batch == 0) return DR_OK;
+  hipStream_t st = S(stream);
+  LsWs w = carve_ls(ws, nnz, batch, nullptr);
+  const int64_t* ind = sp_indices;
+  const int64_t* val = sp_values;
+  const float* wts = sp_weights;
+  const int64_t* n_dev = nullptr;
+  int64_t n_cap = nnz;
+  int rc;
+  if (safe) {
+    const int mode = !prune ? 0 : (sp_weights && combiner != DR_COMBINER_SUM ? 2 : 1);
+    rc = dr_sparse_prune_fill(sp_indices, 2, sp_values, sp_weights, nnz, batch, mode,
+                              default_id >= 0 ? default_id : 0, 1.0f, w.ind, w.val,
+                              sp_weights ? w.w : nullptr, nullptr, w.empty, w.n_dev, w.sub,
+                              w.sub_bytes, stream);
+    if (rc) return rc;
+    ind = w.ind;
+    val = w.val;
+    wts = sp_weights ? w.w : nullptr;
+    n_dev = w.n_dev;
+    n_cap = nnz + batch;
+  }
+  rc = n_dev ? dr_bag_offsets_strided_dev(ind, 2, n_cap, n_dev, batch, w.bag_off, stream)
+             : dr_bag_offsets_strided(ind, 2, n_cap, batch, w.bag_off, stream);
+  if (rc) return rc;
+  const int64_t koff[2] = {0, n_cap};
+  const int64_t* nd[1] = {n_dev};
+  rc = dr_ev_find_grouped(&ev, 1, val, koff, nd, w.rowsel, stream);
+  if (rc) return rc;
+  dr_pool_desc d;
+  memset(&d, 0, sizeof(d));
+  d.pool = dr_ev_pool(ev);
+  d.pool_rows = 1ll << 62;
+  d.ids = w.rowsel;
+  d.default_rows = dr_ev_default_row(ev);
+  d.default_stride = 0;
+  d.bag_off = w.bag_off;
+  d.weights = wts;
+  d.out = out;
+  d.out_stride = out_stride;
+  d.combiner = combiner;
+  d.max_norm = max_norm >= 0.f ? max_norm : -1.f;
+  rc = dr_pool_grouped_ex(&d, 1, batch, dim, DR_ORDER_ALI, vb == 16 ? DR_POOL_BF16 : 0, stream);
+  if (rc) return rc;
+  if (safe && default_id < 0) {
+    hipLaunchKernelGGL(zero_empty_rows_kernel, dim3((unsigned)ceil_div(batch, 4)), dim3(256), 0,
+                       st, out, out_stride, batch, dim, w.empty);
+    DR_LAUNCH_CHECK();
+  }
+  return DR_OK;
+}
+
 }  // extern "C"

@@ -217,6 +217,14 @@ SIGNATURES = {
     "dr_ev_default_row": (_P, [_P]),
     "dr_ev_gather_workspace_size": (_SZ, [_I64]),
     "dr_ev_gather": (_I32, [_P, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "dr_ev_find_grouped": (_I32, [_P, _I32, _P, _P, _P, _P, _P]),
+    "dr_ev_gather_readonly": (_I32, [_P, _P, _I64, _P, _P, _P]),
+    "dr_ev_lookup_onehot_readonly": (_I32, [_P, _I32, _P, _I64, _I64, _I64, _P, _I64, _I32, _I32,
+                                            _P, _P]),
+    "dr_embedding_lookup_sparse_readonly_workspace_size": (_SZ, [_I64, _I64]),
+    "dr_embedding_lookup_sparse_readonly": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _I64, _I64,
+                                                   _I32, _F32, _I32, _I64, _I32, _P, _I64, _P,
+                                                   _SZ, _P]),
     "dr_ev_insert": (_I32, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _P]),
     "dr_ev_insert_synthetic": (_I32, [_P, _I64, _I64, _I64, _U64, _P]),
     "dr_ev_export": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P]),

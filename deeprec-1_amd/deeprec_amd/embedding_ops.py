@@ -17,7 +17,8 @@ import torch
 
 from . import _lib, ops
 from ._lib import COMBINERS, ORDER_ALI, ORDER_SEQ, DrPoolDesc, check, lib, ptr, stream_handle, workspace
-from .kv_variable_ops import EmbeddingVariable, IndexedSlices, PendingRowSlices
+from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
+                               read_only_active)
 
 
 class SparseTensor(object):
@@ -344,6 +345,11 @@ def embedding_stack(x0, params_list, sp_ids_list, combiner="sum"):
         v = sp.values.to(torch.int64).contiguous()
         feats.append(_Feature(p, v, _seg_of(sp), sp.dense_shape[0], None, combiner, None,
                               onehot=_is_onehot(sp, v.numel())))
+    if read_only_active() and all(isinstance(f.params, EmbeddingVariable) for f in feats):
+        # (x0 keeps its own gradient; the embeddings carry none)
+        B, D = x0.shape
+        emb = _run_readonly(feats, ORDER_ALI, None)
+        return torch.cat([x0.float().unsqueeze(1), emb.view(B, len(feats), D)], 1)
     need_grad = torch.is_grad_enabled()
     if _groupable(feats):
         _prepare_group(feats, need_grad)
@@ -821,9 +827,101 @@ def _fused_onehot(feats, order, with_rows=False, out_dtype=None):
     return out
 
 
-def _run(feats, order=ORDER_ALI, need_grad=None, out_dtype=None):
+def _fused_onehot_readonly(feats, order, out_dtype=None):
+    """One-hot read-only lookup in one launch (dr_ev_lookup_onehot_readonly:
+    probe + row copy, absent ids read the default row).  Filter EVs and EVs
+    with a callable initializer qualify: nothing is created, so neither the
+    filter nor the initializer runs.  None when the features do not qualify."""
+    import ctypes as C
+    p0 = feats[0].params
+    B = feats[0].batch
+    T = len(feats)
+    if T > _lib.MAX_GROUP or not all(
+            f.onehot and f.batch == B and f.params.dim == p0.dim and f.params.device == p0.device
+            and f.raw_values.numel() == B and f.params.value_dtype == p0.value_dtype
+            for f in feats):
+        return None
+    W = p0.row_words
+    if not (W % 4 == 0 and W <= 256 and 0 < T * B < (1 << 31)):
+        return None
+    D = p0.dim
+    dev = feats[0].raw_values.device
+    odt = _out_dtype(feats, out_dtype)
+    flags = _lib.LOOKUP_OUT_BF16 if odt == torch.bfloat16 else 0
+    out = torch.empty((B, T * D), dtype=odt, device=dev)
+    handles = (C.c_void_p * T)(*[f.params.handle.value for f in feats])
+    rec = _record_major(feats)
+    if rec is not None:
+        keys, ksb, kst = rec, T, 1
+    else:
+        vals = _concat_values(feats, [t * B for t in range(T + 1)])
+        keys, ksb, kst = ptr(vals), 1, B
+        if _TABLE_ORDER:
+            flags |= _lib.LOOKUP_TABLE_ORDER
+    check(lib().dr_ev_lookup_onehot_readonly(handles, T, keys, ksb, kst, B, ptr(out), T * D, order,
+                                             flags, None, stream_handle(dev)))
+    ops._post(dev)
+    return out
+
+
+def _prepare_readonly(feats):
+    """Unique -> dr_ev_find_grouped -> row per nnz, for <= MAX_GROUP EV
+    features: the row-per-nnz form the pooling kernels take (_desc), with the
+    EV default row for every id that is not served."""
+    import ctypes as C
+    dev = feats[0].values.device
+    T = len(feats)
+    koff = [0]
+    for f in feats:
+        koff.append(koff[-1] + f.values.numel())
+    vals = _concat_values(feats, koff)
+    uniq, idx, _, U = ops.unique_grouped(vals, koff, False)
+    rows = torch.empty(max(koff[-1], 1), dtype=torch.int64, device=dev)
+    rowsel = torch.empty(max(koff[-1], 1), dtype=torch.int64, device=dev)
+    handles = (C.c_void_p * T)(*[f.params.handle.value for f in feats])
+    ndev = (C.c_void_p * T)(*[U.data_ptr() + 8 * t for t in range(T)])
+    check(lib().dr_ev_find_grouped(handles, T, ptr(uniq), ops._koff_array(koff), ndev, ptr(rows),
+                                   stream_handle(dev)))
+    check(lib().dr_rows_per_nnz(ptr(rows), ptr(idx), ops._koff_array(koff), T, ptr(rowsel),
+                                stream_handle(dev)))
+    ops._post(dev)
+    for t, f in enumerate(feats):
+        f.uniq = f.idx = f.rows = f.U = f.defaults = f.group = None
+        f.rowsel = rowsel[koff[t]:koff[t + 1]]
+
+
+def _run_readonly(feats, order, out_dtype):
+    """_run inside read_only_lookups(): the EV features are read without being
+    changed and without a gradient; the others go the usual way, and the
+    columns are put back in feature order."""
+    evs = [f for f in feats if isinstance(f.params, EmbeddingVariable)]
+    if len(evs) != len(feats):
+        other = [f for f in feats if not isinstance(f.params, EmbeddingVariable)]
+        parts = {id(f): None for f in feats}
+        for group, res in ((evs, _run_readonly(evs, order, out_dtype)),
+                           (other, _run(other, order, out_dtype=out_dtype, _plain=True))):
+            col = 0
+            for f in group:
+                d = f.params.dim if not torch.is_tensor(f.params) else f.params.shape[1]
+                parts[id(f)] = res[:, col:col + d]
+                col += d
+        return torch.cat([parts[id(f)] for f in feats], 1)
+    with torch.no_grad():
+        if _FUSED_ONEHOT:
+            out = _fused_onehot_readonly(feats, order, out_dtype)
+            if out is not None:
+                return out
+        for i in range(0, len(feats), _lib.MAX_GROUP):
+            _prepare_readonly(feats[i:i + _lib.MAX_GROUP])
+        return _pool_all(feats, order, out_dtype=out_dtype)
+
+
+def _run(feats, order=ORDER_ALI, need_grad=None, out_dtype=None, _plain=False):
     """Grouped pooled lookup of features sharing the batch -> [B, sum(D_t)]."""
-    tensors = _trainable_tensors(feats) if torch.is_grad_enabled() else []
+    if (not _plain and read_only_active()
+            and any(isinstance(f.params, EmbeddingVariable) for f in feats)):
+        return _run_readonly(feats, order, out_dtype)
+    tensors =_trainable_tensors(feats) if torch.is_grad_enabled() else []
     if need_grad is None:
         need_grad = torch.is_grad_enabled() and (
             bool(tensors) or any(not torch.is_tensor(f.params) for f in feats))
@@ -1015,7 +1113,9 @@ class _PartitionedGatherFn(torch.autograd.Function):
                 sel = perm64[a:b]
                 cnt = None if counts is None else counts.index_select(0, sel)
                 ini = None if init is None else init.index_select(0, sel)
-                dflt = prm._defaults_for(b - a, None) if ini is None else ini
+                # (read-only: the stored default row; the initializer is not called)
+                dflt = ini if ini is not None or read_only_active() else \
+                    prm._defaults_for(b - a, None)
                 emb_part[a:b] = _ev_sparse_read(prm, ids_p, cnt, dflt)
             else:
                 t = prm.weight if isinstance(prm, DenseTable) else prm
@@ -1054,6 +1154,8 @@ class _PartitionedGatherFn(torch.autograd.Function):
 def _ev_sparse_read(ev, ids, counts, defaults):
     """KvResourceGather[V1] of device ids with an explicit [n, D] default
     block (or None = the EV's default row)."""
+    if read_only_active():
+        return ev._sparse_read_readonly(ids, defaults=defaults)
     n = ids.numel()
     out = torch.empty((n, ev.dim), dtype=torch.float32, device=ev.device)
     cnt = None if counts is None else counts.to(torch.int32).contiguous()
@@ -1068,7 +1170,8 @@ def _ev_sparse_read(ev, ids, counts, defaults):
 def _partitioned_gather(params, flat, n_dev, counts, init, strategy):
     tensors = [p for p in params if torch.is_tensor(p) and p.requires_grad]
     anchors = [_anchor(p) for p in params if not torch.is_tensor(p)]
-    if torch.is_grad_enabled() and (anchors or tensors):
+    read_only = read_only_active() and any(isinstance(p, EmbeddingVariable) for p in params)
+    if torch.is_grad_enabled() and (anchors or tensors) and not read_only:
         return _PartitionedGatherFn.apply(anchors[0] if anchors else None, params, flat, n_dev,
                                           counts, init, strategy, *tensors)
     with torch.no_grad():

@@ -161,6 +161,34 @@ def _release_engine(destroy, h):
 atexit.register(lambda: _DEFERRED.clear())   # dropped: the process's device memory goes too
 
 
+# ---------------------------------------------------------------------------
+# Read-only lookups (EmbeddingVar::Lookup, the reference's inference mode)
+# ---------------------------------------------------------------------------
+_READ_ONLY = threading.local()
+
+
+def read_only_active():
+    return getattr(_READ_ONLY, "depth", 0) > 0
+
+
+class read_only_lookups(object):
+    """Context manager (re-entrant, per thread): inside it embedding_lookup,
+    embedding_lookup_sparse[_multi] and safe_embedding_lookup_sparse read
+    EmbeddingVariables without changing them -- evaluation and serving.  A
+    present, admitted id gives its row, any other the EV's default row; no
+    key is created, no sighting counted, no table grown; results carry no
+    grad_fn and nothing is queued in pending_grads.  Dense tables and
+    tensors behave as outside it."""
+
+    def __enter__(self):
+        _READ_ONLY.depth = getattr(_READ_ONLY, "depth", 0) + 1
+        return self
+
+    def __exit__(self, *exc):
+        _READ_ONLY.depth -= 1
+        return False
+
+
 _KEY_DTYPES = (torch.int64, torch.int32)
 # bfloat16: a build-defined bf16 EV (BASELINE configs[4]; the reference
 # registers float and double): bf16 value rows, fp32 optimizer slots
@@ -388,9 +416,17 @@ class EmbeddingVariable(object):
                 n, self.dim).contiguous()
         return None
 
-    def sparse_read(self, indices, counts=None, ev_init_value=None, name=None):
+    def sparse_read(self, indices, counts=None, ev_init_value=None, name=None, read_only=False):
         """KvResourceGather / KvResourceGatherV1 (kv_variable_ops.py:644-664),
-        int32 or int64 ids, float32 or float64 rows per the EV's dtypes."""
+        int32 or int64 ids, float32 or float64 rows per the EV's dtypes.
+
+        read_only (or inside read_only_lookups()): EmbeddingVar::Lookup, the
+        inference mode -- an id that is absent, not admitted by the filter or
+        untouched in this column reads ev_init_value, else the EV's stored
+        default row; nothing is created or counted (`counts` is unused) and a
+        callable initializer is not called."""
+        if read_only or read_only_active():
+            return self._sparse_read_readonly(indices, ev_init_value)
         i32 = indices.dtype == torch.int32
         ids = indices.reshape(-1).to(torch.int32 if i32 else torch.int64).contiguous()
         n = ids.numel()
@@ -412,6 +448,35 @@ class EmbeddingVariable(object):
         from .ops import _post
         _post(self.device)
         return out.reshape(tuple(indices.shape) + (self.dim,))
+
+    def _sparse_read_readonly(self, indices, ev_init_value=None, defaults=None):
+        # (the C entry takes int64 keys: int32 ids are widened here)
+        ids = indices.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        n = ids.numel()
+        out = torch.empty((n, self.dim), dtype=self.value_dtype, device=self.device)
+        if n:
+            if defaults is None and ev_init_value is not None:
+                defaults = torch.as_tensor(ev_init_value, dtype=self.value_dtype,
+                                           device=self.device).expand(n, self.dim).contiguous()
+            check(lib().dr_ev_gather_readonly(self._h, ptr(ids), n, ptr(defaults), ptr(out),
+                                              stream_handle(self.device)))
+            from .ops import _post
+            _post(self.device)
+        return out.reshape(tuple(indices.shape) + (self.dim,))
+
+    def find(self, keys, n_dev=None):
+        """Read-only resolve of keys to rows: -(i+1) = serve the default for
+        key i (absent, not admitted, or this column untouched).  The EV is
+        left exactly as it was."""
+        keys = keys.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        n = keys.numel()
+        rows = torch.empty(n, dtype=torch.int64, device=self.device)
+        handles = (C.c_void_p * 1)(self._h.value)
+        koff = (C.c_int64 * 2)(0, n)
+        nd = None if n_dev is None else (C.c_void_p * 1)(n_dev.data_ptr())
+        check(lib().dr_ev_find_grouped(handles, 1, ptr(keys), koff, nd, ptr(rows),
+                                       stream_handle(self.device)))
+        return rows
 
     def resolve(self, keys, n_dev=None, counts=None, defaults=None):
         """Insert-on-miss resolve of (unique) keys to rows; -(i+1) = default row i."""

@@ -29,6 +29,8 @@ import os
 import torch
 
 from . import ops
+from ._lib import INVALID_ARGUMENT, DeepRecError
+from .kv_variable_ops import read_only_active
 from .embedding_ops import SparseTensor, embedding_lookup_sparse_multi, embedding_stack
 
 
@@ -362,6 +364,12 @@ def _sharded_lookup(anchor, engine, ids):
     """The engine's lookup as an autograd node when gradients are recorded;
     under torch.no_grad() (an eval pass) a plain forward that keeps no
     routing state (need_grad off: the engines' cheaper direct path)."""
+    if read_only_active():
+        # the engines' owner side is insert-on-miss: serving here would create
+        # and count keys behind a context that promises not to
+        raise DeepRecError(INVALID_ARGUMENT,
+                           "read_only_lookups(): the sharded lookup engines have no read-only "
+                           "forward yet; evaluate on a local (unsharded) model")
     if torch.is_grad_enabled():
         return _ShardedLookupFn.apply(anchor, engine, ids)
     # this forward overwrites the engine's exchange buffers too: a pending

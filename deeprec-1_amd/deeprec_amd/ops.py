@@ -286,10 +286,11 @@ def sort_pairs(keys, vals, bit_hi, bit_lo=0):
 # ---------------------------------------------------------------------------
 def embedding_lookup_sparse_c(params, sp_indices, sp_values, batch, sp_weights=None,
                               combiner="mean", max_norm=None, safe=False, default_id=None,
-                              prune=True):
+                              prune=True, read_only=False):
     """params: an EmbeddingVariable (handle / dim attributes) or a dense fp32
     [rows, dim] tensor.  sp_indices [nnz, 2] int64 rows-sorted, sp_values
-    [nnz] int64, sp_weights [nnz] fp32 or None.  Returns [batch, dim]."""
+    [nnz] int64, sp_weights [nnz] fp32 or None.  Returns [batch, dim].
+    read_only: dr_embedding_lookup_sparse_readonly (an EV, left unchanged)."""
     ind = sp_indices.to(torch.int64).contiguous()
     val = sp_values.to(torch.int64).contiguous()
     w = None if sp_weights is None else sp_weights.to(torch.float32).contiguous()
@@ -301,9 +302,10 @@ def embedding_lookup_sparse_c(params, sp_indices, sp_values, batch, sp_weights=N
     else:
         ev, table, rows, dim = params.handle, None, 0, params.dim
     out = torch.empty((batch, dim), dtype=torch.float32, device=dev)
-    wsb = lib().dr_embedding_lookup_sparse_workspace_size(nnz, batch)
+    entry = "dr_embedding_lookup_sparse_readonly" if read_only else "dr_embedding_lookup_sparse"
+    wsb = getattr(lib(), entry + "_workspace_size")(nnz, batch)
     ws = workspace(wsb, dev)
-    check(lib().dr_embedding_lookup_sparse(
+    check(getattr(lib(), entry)(
         ev, ptr(table), rows, dim, ptr(ind), ptr(val), ptr(w), nnz, batch, COMBINERS[combiner],
         -1.0 if max_norm is None else float(max_norm), 1 if safe else 0,
         -1 if default_id is None else int(default_id), 1 if prune else 0, ptr(out), dim,

@@ -203,6 +203,28 @@ def _(resource, indices, dim, default_value=None, counts=None):
     return indices.new_empty(tuple(indices.shape) + (dim,), dtype=torch.float32)
 
 
+@custom_op(_NS + "::kv_resource_gather_readonly", mutates_args=(), device_types="cuda")
+def kv_resource_gather_readonly(resource: Tensor, indices: Tensor, dim: int,
+                                default_value: Optional[Tensor] = None) -> Tensor:
+    """EmbeddingVar::Lookup (inference mode): rows of `indices`; an id that is
+    absent, not admitted or untouched in this column reads default_value
+    ([n, dim]) or the EV default.  The EV is not changed (mutates_args=())."""
+    ids = indices.reshape(-1).to(torch.int64).contiguous()
+    n = ids.numel()
+    out = torch.empty((n, dim), dtype=torch.float32, device=ids.device)
+    if n:
+        dflt = None if default_value is None else default_value.to(torch.float32).contiguous()
+        check(lib().dr_ev_gather_readonly(_hr(resource), ptr(ids), n, ptr(dflt), ptr(out),
+                                          stream_handle(ids.device)))
+        ops._post(ids.device)
+    return out.reshape(tuple(indices.shape) + (dim,))
+
+
+@kv_resource_gather_readonly.register_fake
+def _(resource, indices, dim, default_value=None):
+    return indices.new_empty(tuple(indices.shape) + (dim,), dtype=torch.float32)
+
+
 @custom_op(_NS + "::kv_resource_insert", mutates_args=("resource",), device_types="cuda")
 def kv_resource_insert(resource: Tensor, keys: Tensor, values: Tensor,
                        versions: Optional[Tensor] = None, freqs: Optional[Tensor] = None,
@@ -599,6 +621,7 @@ dot_interaction.register_autograd(_dot_backward, setup_context=_save_first)
 
 OPS = ["unique_with_counts", "sparse_segment_reduce", "sparse_segment_reduce_grad",
        "unsorted_segment_sum", "resource_gather", "kv_resource_gather", "kv_resource_insert",
+       "kv_resource_gather_readonly",
        "kv_resource_sparse_apply_gradient_descent", "kv_resource_sparse_apply_adagrad",
        "kv_resource_sparse_apply_adam", "kv_resource_sparse_apply_ftrl",
        "kv_resource_sparse_apply_adam_async", "kv_resource_sparse_apply_adagrad_decay",

@@ -495,6 +495,41 @@ int dr_ev_gather(dr_ev* ev, const int64_t* keys, int64_t n, const float* default
                  const int32_t* counts, float* out, void* ws, size_t ws_bytes,
                  void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Read-only lookups (EmbeddingVar::Lookup, the reference's inference mode,  */
+/* embedding_var.h): evaluation and serving.  A key is served its stored row */
+/* iff it is in the map with a published, live row, this column's first-     */
+/* touch bit is set and, for a Counter-filter EV, freq[row] >= filter_freq;  */
+/* otherwise a default is served.  Nothing is created, counted or stamped:   */
+/* slots, rc bits, the row counter, freq, version, Bloom counters (neither   */
+/* read nor written: membership in the map decides), value pools and the     */
+/* host capacity accounting are left as they are, and the table never grows. */
+/* Key -1 uses its special slot.  Ordering against a writer on another       */
+/* stream is the caller's business, as for every other lookup.  The tables'  */
+/* pointers are passed by value: a captured call is valid until a table next */
+/* grows.                                                                    */
+/* ------------------------------------------------------------------------ */
+/* Grouped find: keys / rows_out concatenated, table t at [koff_host[t],     */
+/* koff_host[t+1]), optional per-table DEVICE counts (the grouping of        */
+/* dr_ev_resolve_grouped; the EVs need not share dim).  rows_out[i] = row,   */
+/* or -(li+1), li = i - koff_host[t], when the default is to be served.      */
+int dr_ev_find_grouped(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                       const int64_t* koff_host, const int64_t* const* n_dev_per_table,
+                       int64_t* rows_out, void* stream);
+/* Gather: out[i] = the row of keys[i], or defaults[i] ([n, dim], nullable:  */
+/* the EV's default row).  defaults / out are float, double or bf16 per the  */
+/* EV's value_bits.                                                          */
+int dr_ev_gather_readonly(dr_ev* ev, const int64_t* keys, int64_t n, const void* defaults,
+                          void* out, void* stream);
+/* Fused one-hot lookup (arguments and DR_LOOKUP_* flags of                  */
+/* dr_ev_lookup_onehot_ex; no workspace).  One kernel: a key that is not     */
+/* served reads its table's default row, rows_out (nullable) gets -1 for it. */
+/* Counter / Bloom EVs are accepted.                                         */
+int dr_ev_lookup_onehot_readonly(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                                 int64_t key_stride_bag, int64_t key_stride_table,
+                                 int64_t batch, void* out, int64_t out_stride, int order,
+                                 int flags, int64_t* rows_out, void* stream);
+
 /* KvResourceInsert / KvResourceImportV2 with EmbeddingVar::Import semantics */
 /* (embedding_var.h:187-219): partition_num <= 0 disables the               */
 /* key % 1000 % partition_num == partition_id filter.                        */
@@ -1315,6 +1350,20 @@ int dr_embedding_lookup_sparse(dr_ev* ev, const float* table, int64_t table_rows
                                float max_norm, int safe, int64_t default_id, int prune,
                                float* out, int64_t out_stride, void* ws, size_t ws_bytes,
                                void* stream);
+/* The same over an EV read-only (see dr_ev_find_grouped): the same          */
+/* arguments and output contract, `ev` required and `table` NULL (a binding  */
+/* switches by name); absent / unadmitted ids pool the EV's default row and  */
+/* the EV is left unchanged.  Every id is probed as it stands (a read-only   */
+/* probe has no counts to merge, so the filter-EV Unique and its host        */
+/* synchronisation drop out): no host synchronisation at all.                */
+size_t dr_embedding_lookup_sparse_readonly_workspace_size(int64_t nnz, int64_t batch);
+int dr_embedding_lookup_sparse_readonly(dr_ev* ev, const float* table, int64_t table_rows,
+                                        int dim, const int64_t* sp_indices,
+                                        const int64_t* sp_values, const float* sp_weights,
+                                        int64_t nnz, int64_t batch, int combiner,
+                                        float max_norm, int safe, int64_t default_id, int prune,
+                                        float* out, int64_t out_stride, void* ws,
+                                        size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Checkpoint support (host function, no device work): crc32c::Extend of    */
