@@ -90,11 +90,13 @@ __global__ void fill_synth_tail_kernel(float* __restrict__ t, int64_t begin, int
 
 
 // ---- measurement hook: HIP events around one kernel's launches ------------
-// dr_kernel_timing(which) arms it (DR_TIME_LOOKUP: ev_lookup_onehot_kernel,
-// DR_TIME_POOL_ONEHOT: pool_onehot_kernel); every such launch on any stream
-// is then bracketed by a pair of events recorded on that launch's stream,
-// and dr_kernel_timing_result sums their elapsed times -- the kernel's own
-// duration, not the surrounding helper launches.  Off: one branch per launch.
+// dr_kernel_timing(which) arms it (DR_TIME_LOOKUP: the fused lookup's
+// ev_lookup_line_kernel / ev_lookup_onehot_kernel and the read-only
+// ev_lookup_ro_kernel, DR_TIME_POOL_ONEHOT: pool_onehot_kernel); every such
+// launch on any stream is then bracketed by a pair of events recorded on that
+// launch's stream, and dr_kernel_timing_result sums their elapsed times --
+// the kernel's own duration, not the surrounding helper launches.  Off: one
+// branch per launch.
 static std::mutex g_tmu;
 static int g_time_which = 0;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_tev;

@@ -45,6 +45,8 @@ struct __attribute__((aligned(16))) Slot {
   uint64_t key;
   uint64_t rc;
 };
+// a slot as one 16-byte load: .x = key, .y = rc
+typedef unsigned long long slot_v __attribute__((ext_vector_type(2)));
 
 struct EvShared {
   std::atomic<int> refs{1};
@@ -238,7 +240,6 @@ __device__ Slot* ev_find(const EvDesc& e, uint64_t key, bool insert, bool* creat
       }
       Slot* c = e.slots + probe_slot(h0, (uint64_t)probes, mask);
       // one 16-byte load brings key and rc: a hit needs no second round trip
-      typedef unsigned long long slot_v __attribute__((ext_vector_type(2)));
       const slot_v sv = *reinterpret_cast<const slot_v*>(c);
       uint64_t cur = sv.x;
       if (cur == key) {
@@ -1813,21 +1814,80 @@ struct LkDesc {
   uint64_t colbit;
 };
 
-struct LookupArgs {
-  LkDesc d[DR_MAX_GROUP];
+static LkDesc make_lk_desc(const dr_ev* ev) {
+  const EvShared* s = ev->sh;
+  LkDesc d;
+  d.slots = s->slots;
+  d.cap = s->cap;
+  d.pool = s->pools[ev->col];
+  d.colbit = 1ull << (48 + ev->col);
+  return d;
+}
+
+// Ids, output and row record of a fused one-hot lookup (training and
+// read-only alike).
+struct LkIo {
   const int64_t* keys;  // id of (bag b, table t) = keys[b * ksb + t * kst]
   int64_t ksb, kst;     // [T, B] feature-major: (1, B); [B, T] record-major: (T, 1)
   float* out;
-  int64_t out_stride;
+  int64_t out_stride;   // float words
   int64_t* rows;        // [T, B] row served per id (-1: default), or nullptr
   int tmaj;             // visit slots table by table (s = t * B + b), not in output order
   int rrec;             // rows record-major: rows[b * T + t] (DR_LOOKUP_ROWS_RECORD)
 };
 
+static LkIo make_lk_io(const int64_t* keys, int64_t ksb, int64_t kst, float* out,
+                       int64_t out_stride, int64_t* rows, int flags) {
+  LkIo io;
+  io.keys = keys;
+  io.ksb = ksb;
+  io.kst = kst;
+  io.out = out;
+  io.out_stride = out_stride;
+  io.rows = rows;
+  io.tmaj = (flags & DR_LOOKUP_TABLE_ORDER) ? 1 : 0;
+  io.rrec = (flags & DR_LOOKUP_ROWS_RECORD) ? 1 : 0;
+  return io;
+}
+
+struct LookupArgs {
+  LkDesc d[DR_MAX_GROUP];
+  LkIo io;
+};
+
+// Slot s -> (bag, table) in the visiting order (T * B < 2^31: host check).
+__device__ __forceinline__ void slot_bt(int64_t s, int T, int64_t B, int tmaj, int64_t* b, int* t) {
+  const uint32_t dv = tmaj ? (uint32_t)B : (uint32_t)T;
+  const uint32_t q = (uint32_t)s / dv, r = (uint32_t)s - q * dv;
+  *b = tmaj ? (int64_t)r : (int64_t)q;
+  *t = tmaj ? (int)q : (int)r;
+}
+
+// The 64-bit row address held by lane `src`, on every lane.
+__device__ __forceinline__ const float* bcast_row_ptr(uint64_t u, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)u, src, 64);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(u >> 32), src, 64);
+  return reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo));
+}
+
+// Wave-aggregated append of the lanes with `missed` to the miss list: one
+// atomic per wave.  (The list holds output-order slots b * T + t.)
+__device__ __forceinline__ void miss_append(bool missed, int64_t slot, int lane,
+                                            int32_t* __restrict__ mlist,
+                                            unsigned long long* __restrict__ mcnt) {
+  const uint64_t mm = __ballot(missed);
+  if (mm) {
+    const int leader = __ffsll((unsigned long long)mm) - 1;
+    unsigned long long at = 0;
+    if (lane == leader) at = atomicAdd(mcnt, (unsigned long long)__popcll(mm));
+    at = __shfl(at, leader, 64);
+    if (missed) mlist[at + __popcll(mm & lanemask_lt())] = (int32_t)slot;
+  }
+}
+
 // Row of `key` when present with this column initialised, else -1.
 __device__ __forceinline__ int64_t ev_probe_row(const LkDesc& e, uint64_t key) {
   uint64_t rc;
-  typedef unsigned long long slot_v __attribute__((ext_vector_type(2)));
   if (key == kEmptyKey) {
     const slot_v sv = gld(reinterpret_cast<const slot_v*>(e.slots + e.cap));
     if (sv.x != 0ull) return -1;
@@ -1854,7 +1914,7 @@ __device__ __forceinline__ int64_t ev_probe_row(const LkDesc& e, uint64_t key) {
 // WIDEN: bf16 rows (a bf16 EV) widened into an fp32 output -- `dim` counts
 // values, rows are dim / 2 float words apart.  (A bf16 output is the plain
 // kernel on float words.)
-template <int VEC, int G, int CPL, int ORDER, int NB, bool WIDEN = false>
+template <int VEC, int G, int ORDER, int NB, bool WIDEN = false>
 __global__ __launch_bounds__(256) void ev_lookup_onehot_kernel(LookupArgs a, int T, int64_t B,
                                                                int dim, int32_t* __restrict__ mlist,
                                                                unsigned long long* __restrict__ mcnt) {
@@ -1871,15 +1931,9 @@ __global__ __launch_bounds__(256) void ev_lookup_onehot_kernel(LookupArgs a, int
   int pt = 0;
   uint64_t pkey = 0;
   if (prober) {
-    const int64_t s = s0 + lg;
-    if (a.tmaj) {   // slots < 2^31 (host check)
-      pt = (int)((uint32_t)s / (uint32_t)B);
-      pb = s - (int64_t)pt * B;
-    } else {
-      pb = (int64_t)((uint32_t)s / (uint32_t)T);
-      pt = (int)(s - pb * T);
-    }
-    pkey = (uint64_t)__builtin_nontemporal_load(gp(a.keys + pb * a.ksb + (int64_t)pt * a.kst));
+    slot_bt(s0 + lg, T, B, a.io.tmaj, &pb, &pt);
+    pkey = (uint64_t)__builtin_nontemporal_load(
+        gp(a.io.keys + pb * a.io.ksb + (int64_t)pt * a.io.kst));
   }
   if (threadIdx.x < T) sd[threadIdx.x] = a.d[threadIdx.x];
   __syncthreads();
@@ -1896,59 +1950,38 @@ __global__ __launch_bounds__(256) void ev_lookup_onehot_kernel(LookupArgs a, int
     const int64_t row = ev_probe_row(e, pkey);
     if (row >= 0) {
       mine = e.pool + row * (int64_t)(WIDEN ? dim / 2 : dim);
-      if (a.rows) a.rows[a.rrec ? b * T + t : (int64_t)t * B + b] = row;
+      if (a.io.rows) a.io.rows[a.io.rrec ? b * T + t : (int64_t)t * B + b] = row;
     } else {
       missed = true;
     }
   }
-  // wave-aggregated append of the misses
-  const uint64_t mm = __ballot(missed);
-  if (mm) {
-    const int lane = (int)(threadIdx.x % 64);
-    const int leader = __ffsll((unsigned long long)mm) - 1;
-    unsigned long long at = 0;
-    if (lane == leader) at = atomicAdd(mcnt, (unsigned long long)__popcll(mm));
-    at = __shfl(at, leader, 64);
-    // (the miss list holds output-order slots b * T + t in either visiting order)
-    if (missed) mlist[at + __popcll(mm & lanemask_lt())] = (int32_t)(pb * T + pt);
-  }
+  // (output-order slot b * T + t in either visiting order)
+  miss_append(missed, pb * T + pt, (int)(threadIdx.x % 64), mlist, mcnt);
   // every row address first (the shuffles' LDS waits then precede the row
   // loads), then the NB row loads back to back as global (not flat) loads
   const float* p[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) {
-    const uint64_t u = (uint64_t)(uintptr_t)mine;
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)u, base + q, 64);
-    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(u >> 32), base + q, 64);
-    p[q] = reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo));
-  }
-  Row<VEC, G, CPL> x[NB];
+  for (int q = 0; q < NB; ++q) p[q] = bcast_row_ptr((uint64_t)(uintptr_t)mine, base + q);
+  Row<VEC, G, 1> x[NB];
   float* o[NB];
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
     const int64_t s = s0 + q;
     o[q] = nullptr;
     if (p[q] && s < slots) {
-      int64_t b, t;
-      if (a.tmaj) {
-        t = (int64_t)((uint32_t)s / (uint32_t)B);
-        b = s - t * B;
-      } else {
-        b = (int64_t)((uint32_t)s / (uint32_t)T);
-        t = s - b * T;
-      }
-      o[q] = a.out + b * a.out_stride + t * (int64_t)dim;
+      int64_t b;
+      int t;
+      slot_bt(s, T, B, a.io.tmaj, &b, &t);
+      o[q] = a.io.out + b * a.io.out_stride + (int64_t)t * dim;
     }
-    load_row_copy<VEC, G, CPL, WIDEN>(x[q], p[q], lg, dv);
+    load_row_copy<VEC, G, 1, WIDEN>(x[q], p[q], lg, dv);
   }
   wait_loads();
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
-    if (ORDER == DR_ORDER_SEQ) {  // fused op: out = 0 + e (-0.0 -> +0.0)
-#pragma unroll
-      for (int c = 0; c < CPL; ++c) x[q].v[c] = vadd(vzero<typename VecT<VEC>::T>(), x[q].v[c]);
-    }
-    if (o[q]) store_row_nt<VEC, G, CPL>(x[q], o[q], lg, dv);
+    if (ORDER == DR_ORDER_SEQ)  // fused op: out = 0 + e (-0.0 -> +0.0)
+      x[q].v[0] = vadd(vzero<typename VecT<VEC>::T>(), x[q].v[0]);
+    if (o[q]) store_row_nt<VEC, G, 1>(x[q], o[q], lg, dv);
   }
 }
 
@@ -1960,16 +1993,14 @@ __global__ __launch_bounds__(256) void ev_lookup_onehot_kernel(LookupArgs a, int
 // bench's load), which the slot-by-slot walk paid as an extra L2 round trip
 // in most waves.
 // ---------------------------------------------------------------------------
-typedef unsigned long long slot_v2 __attribute__((ext_vector_type(2)));
-
 // Issue half: lane j (= lane % 8) of the key's 8 lanes loads slot j of the
 // home line (key -1: its special slot, on all 8 lanes).  Branch-free: the
 // address is a select, the load is unconditional.
-__device__ __forceinline__ slot_v2 line_probe_issue(const Slot* slots, int64_t cap, uint64_t key,
+__device__ __forceinline__ slot_v line_probe_issue(const Slot* slots, int64_t cap, uint64_t key,
                                                     int j) {
   const uint64_t line = (mix64(key) & (uint64_t)(cap - 1)) & ~7ull;
   const uint64_t at = key == kEmptyKey ? (uint64_t)cap : line + (uint64_t)j;
-  return gld(reinterpret_cast<const slot_v2*>(slots + at));
+  return gld(reinterpret_cast<const slot_v*>(slots + at));
 }
 
 // Resolve half: every lane of the wave calls it (ballots, shuffles).  Each
@@ -1977,7 +2008,7 @@ __device__ __forceinline__ slot_v2 line_probe_issue(const Slot* slots, int64_t c
 // dead row: the miss path).  A key neither found nor ruled out in its home
 // line (a full line, ~0.5 % at the bench's load) walks on from probe 8.
 __device__ __forceinline__ int64_t line_probe_resolve(const Slot* slots, int64_t cap,
-                                                      uint64_t colbit, uint64_t key, slot_v2 sv,
+                                                      uint64_t colbit, uint64_t key, slot_v sv,
                                                       int lane) {
   const int j = lane & 7;
   const bool special = key == kEmptyKey;
@@ -2004,7 +2035,7 @@ __device__ __forceinline__ int64_t line_probe_resolve(const Slot* slots, int64_t
   if (!((rh >> f) & 1u)) rc = kUnset;  // an empty slot comes first, or nothing settled
   if (!any) {  // the home line holds 8 other keys: continue the sequence
     for (uint64_t i = 8; i <= (uint64_t)cap; ++i) {
-      const slot_v2 w = gld(reinterpret_cast<const slot_v2*>(slots + probe_slot(h0, i, mask)));
+      const slot_v w = gld(reinterpret_cast<const slot_v*>(slots + probe_slot(h0, i, mask)));
       if (w.x == key) {
         rc = w.y;
         break;
@@ -2022,42 +2053,34 @@ __device__ __forceinline__ int64_t line_probe_resolve(const Slot* slots, int64_t
 // are not stored read row 0), the store target a select (rows that must not
 // be written go to a junk line of the workspace).  A branch around a load
 // makes hipcc wait for it right there; a branch around a store makes the
-// counted waits of a software pipeline path-dependent (vmcnt(0)).
-template <int VEC, int G, int CPL, bool WIDEN>
-__device__ __forceinline__ void load_row_copy_u(Row<VEC, G, CPL>& x, const float* p, int lg,
+// waits after it path-dependent (vmcnt(0)).
+template <int VEC, int G, bool WIDEN>
+__device__ __forceinline__ void load_row_copy_u(Row<VEC, G, 1>& x, const float* p, int lg,
                                                 int dv) {
-#pragma unroll
-  for (int c = 0; c < CPL; ++c) {
-    int col = lg + c * G;
-    col = col < dv ? col : dv - 1;
-    if constexpr (WIDEN) {
-      typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-      const u2 w = __builtin_nontemporal_load(gp(reinterpret_cast<const u2*>(p) + col));
-      const float2 a = bf16x2_to_f2(w.x), b = bf16x2_to_f2(w.y);
-      x.v[c] = make_float4(a.x, a.y, b.x, b.y);
-    } else {
-      x.v[c] = nt_load(reinterpret_cast<const typename VecT<VEC>::T*>(p) + col);
-    }
+  const int col = lg < dv ? lg : dv - 1;
+  if constexpr (WIDEN) {
+    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+    const u2 w = __builtin_nontemporal_load(gp(reinterpret_cast<const u2*>(p) + col));
+    const float2 a = bf16x2_to_f2(w.x), b = bf16x2_to_f2(w.y);
+    x.v[0] = make_float4(a.x, a.y, b.x, b.y);
+  } else {
+    x.v[0] = nt_load(reinterpret_cast<const typename VecT<VEC>::T*>(p) + col);
   }
 }
 
-template <int VEC, int G, int CPL, int ORDER>
-__device__ __forceinline__ void store_row_sel(Row<VEC, G, CPL>& x, float* p, float* junk, int lg,
+template <int VEC, int G, int ORDER>
+__device__ __forceinline__ void store_row_sel(Row<VEC, G, 1>& x, float* p, float* junk, int lg,
                                               int dv) {
-#pragma unroll
-  for (int c = 0; c < CPL; ++c) {
-    const int col = lg + c * G;
-    if (ORDER == DR_ORDER_SEQ) x.v[c] = vadd(vzero<typename VecT<VEC>::T>(), x.v[c]);  // 0 + e
-    float* dst = col < dv ? p + (int64_t)col * VEC : junk + 2048 + (int64_t)(lg % 64) * VEC;
-    nt_store(x.v[c], reinterpret_cast<typename VecT<VEC>::T*>(dst));
-  }
+  if (ORDER == DR_ORDER_SEQ) x.v[0] = vadd(vzero<typename VecT<VEC>::T>(), x.v[0]);  // 0 + e
+  float* dst = lg < dv ? p + (int64_t)lg * VEC : junk + 2048 + (int64_t)(lg % 64) * VEC;
+  nt_store(x.v[0], reinterpret_cast<typename VecT<VEC>::T*>(dst));
 }
 
 // Output-order lookup with line-wide probes: a wave owns 8 consecutive
 // output slots (key k of the wave on lanes 8k..8k+7); each group of G = 8 NB
 // lanes then copies NB of the 8 rows (row q of group g = the key on lane
 // g G + 8 q).  One-shot: key -> line -> rows -> stores per wave.
-template <int VEC, int G, int CPL, int ORDER, bool WIDEN = false>
+template <int VEC, int G, int ORDER, bool WIDEN = false>
 __global__ __launch_bounds__(256) void ev_lookup_line_kernel(LookupArgs a, int T, int64_t B,
                                                              int dim, int32_t* __restrict__ mlist,
                                                              unsigned long long* __restrict__ mcnt,
@@ -2070,12 +2093,12 @@ __global__ __launch_bounds__(256) void ev_lookup_line_kernel(LookupArgs a, int T
   const int64_t ws0 = ((int64_t)blockIdx.x * 4 + threadIdx.x / 64) * 8;  // wave's first slot
   const int64_t s = ws0 + (lane >> 3);
   const bool valid = s < slots;
-  const int64_t sc = valid ? s : slots - 1;
-  const int64_t b = (int64_t)((uint32_t)sc / (uint32_t)T);
-  const int t = (int)(sc - b * T);
+  int64_t b;
+  int t;
+  slot_bt(valid ? s : slots - 1, T, B, 0, &b, &t);
   // the id's round trip overlaps the descriptor staging (ids read once)
   const uint64_t key =
-      (uint64_t)__builtin_nontemporal_load(gp(a.keys + b * a.ksb + (int64_t)t * a.kst));
+      (uint64_t)__builtin_nontemporal_load(gp(a.io.keys + b * a.io.ksb + (int64_t)t * a.io.kst));
   if (threadIdx.x < T) sd[threadIdx.x] = a.d[threadIdx.x];
   __syncthreads();
   if (ws0 >= slots) return;  // whole waves
@@ -2084,16 +2107,8 @@ __global__ __launch_bounds__(256) void ev_lookup_line_kernel(LookupArgs a, int T
   const int64_t row = line_probe_resolve(tsl, tcap, sd[t].colbit, key,
                                          line_probe_issue(tsl, tcap, key, lane & 7), lane);
   const bool head = (lane & 7) == 0 && valid;
-  const bool missed = head && row < 0;
-  if (head && row >= 0 && a.rows) a.rows[a.rrec ? s : (int64_t)t * B + b] = row;
-  const uint64_t mm = __ballot(missed);
-  if (mm) {
-    const int leader = __ffsll((unsigned long long)mm) - 1;
-    unsigned long long at = 0;
-    if (lane == leader) at = atomicAdd(mcnt, (unsigned long long)__popcll(mm));
-    at = __shfl(at, leader, 64);
-    if (missed) mlist[at + __popcll(mm & lanemask_lt())] = (int32_t)s;
-  }
+  if (head && row >= 0 && a.io.rows) a.io.rows[a.io.rrec ? s : (int64_t)t * B + b] = row;
+  miss_append(head && row < 0, s, lane, mlist, mcnt);
   const int64_t rstride = WIDEN ? dim / 2 : dim;
   const uint64_t mine = (uint64_t)(uintptr_t)(sd[t].pool + (row >= 0 ? row : 0) * rstride);
   const uint64_t okm = __ballot(valid && row >= 0);
@@ -2101,144 +2116,19 @@ __global__ __launch_bounds__(256) void ev_lookup_line_kernel(LookupArgs a, int T
   const int dv = dim / VEC;
   const float* p[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)mine, base + 8 * q, 64);
-    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(mine >> 32), base + 8 * q, 64);
-    p[q] = reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo));
-  }
-  Row<VEC, G, CPL> x[NB];
+  for (int q = 0; q < NB; ++q) p[q] = bcast_row_ptr(mine, base + 8 * q);
+  Row<VEC, G, 1> x[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) load_row_copy_u<VEC, G, CPL, WIDEN>(x[q], p[q], lg, dv);
+  for (int q = 0; q < NB; ++q) load_row_copy_u<VEC, G, WIDEN>(x[q], p[q], lg, dv);
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
-    const int64_t sq = ws0 + (base / G) * NB + q;
-    const int64_t bq = (int64_t)((uint32_t)sq / (uint32_t)T);
-    const int64_t tq = sq - bq * T;
-    float* dst = ((okm >> (base + 8 * q)) & 1ull) ? a.out + bq * a.out_stride + tq * (int64_t)dim
-                                                  : junk + q * 256;
-    store_row_sel<VEC, G, CPL, ORDER>(x[q], dst, junk, lg, dv);
-  }
-}
-
-// Software-pipelined persistent form of the same lookup: each wave walks its
-// items (8 output slots each) with the keys of item k+2 and the home-line
-// probes of item k+1 in flight while the rows of item k load and the rows of
-// item k-1 are stored -- the probe's dependent round trip leaves the row
-// stream's critical path.  Issue order per iteration: rows(k), probes(k+1),
-// keys(k+2), then the NB stores of k-1; every one of them unconditional, so
-// the wait at the loop top for probes(k+1) is vmcnt(1 + NB stores) on every
-// path and never waits for the stores just issued.  XCD-major item ranges
-// (blocks b, b + 8, ... run on one XCD: speed only, any placement is correct).
-template <int VEC, int G, int CPL, int ORDER, bool WIDEN = false>
-__global__ __launch_bounds__(256) void ev_lookup_pipe_kernel(LookupArgs a, int T, int64_t B,
-                                                             int dim, int32_t* __restrict__ mlist,
-                                                             unsigned long long* __restrict__ mcnt,
-                                                             float* __restrict__ junk) {
-  constexpr int NB = G / 8;
-  static_assert(NB * 8 == G, "8 lanes per key, 8 keys per wave");
-  __shared__ LkDesc sd[DR_MAX_GROUP];
-  if (threadIdx.x < T) sd[threadIdx.x] = a.d[threadIdx.x];
-  __syncthreads();
-  const uint32_t slots = (uint32_t)((int64_t)T * B);  // < 2^31 (host check)
-  const uint32_t items = (slots + 7) / 8;
-  const int lane = (int)(threadIdx.x & 63);
-  const int kq = lane >> 3, j = lane & 7;
-  const int lg = lane % G, base = lane - lg;
-  const int dv = dim / VEC;
-  const int64_t rstride = WIDEN ? dim / 2 : dim;
-  const uint32_t LW = (gridDim.x / 8) * 4;  // waves per XCD (grid % 8 == 0)
-  const uint32_t per = (items + 7) / 8;
-  const uint32_t i0 = (blockIdx.x % 8) * per;
-  const uint32_t i1 = i0 + per < items ? i0 + per : items;
-  uint32_t it = i0 + (blockIdx.x / 8) * 4 + threadIdx.x / 64;
-  if (it >= i1) return;  // whole waves
-  const uint32_t T32 = (uint32_t)T;
-  // slot of this lane's key in item `item` (clamped: reads past the range
-  // are harmless and keep the loop free of branches)
-  auto slot_of = [&](uint32_t item) -> uint32_t {
-    const uint32_t s = item * 8 + kq;
-    return s < slots ? s : slots - 1;
-  };
-  auto key_at = [&](uint32_t s) -> uint64_t {
-    const uint32_t b = s / T32, t = s - b * T32;
-    return (uint64_t)__builtin_nontemporal_load(
-        gp(a.keys + (int64_t)b * a.ksb + (int64_t)t * a.kst));
-  };
-  uint32_t sA = slot_of(it);
-  uint64_t kA = key_at(sA);
-  uint32_t tA = sA % T32;
-  slot_v2 svA = line_probe_issue(sd[tA].slots, sd[tA].cap, kA, j);
-  uint32_t sB = slot_of(it + LW);
-  uint64_t kB = key_at(sB);
-  // rows in flight / being stored ping-pong between X0 and X1 (the loop is
-  // unrolled twice: no register copy of a pending load)
-  Row<VEC, G, CPL> X0[NB], X1[NB];
-#pragma unroll
-  for (int q = 0; q < NB; ++q)
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) X1[q].v[c] = vzero<typename VecT<VEC>::T>();
-  uint64_t okp = 0;  // which rows of the previous item to store (bit = key lane)
-  uint32_t itp = it;
-  auto store_item = [&](Row<VEC, G, CPL>(&xs)[NB]) {
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t sq = itp * 8 + (uint32_t)((base / G) * NB + q);
-      const uint32_t bq = sq / T32, tq = sq - bq * T32;
-      float* dst = ((okp >> (base + 8 * q)) & 1ull)
-                       ? a.out + (int64_t)bq * a.out_stride + (int64_t)tq * dim
-                       : junk + q * 256;  // distinct lines: no store merged away
-      store_row_sel<VEC, G, CPL, ORDER>(xs[q], dst, junk, lg, dv);
-    }
-  };
-  // the loop's shape on entry too: NB (junk) stores after the first probes
-  store_item(X1);
-  // one item: settle its probes, issue its rows into xl, the probes of the
-  // next item and the keys of the one after, then store xs (previous item)
-  auto step = [&](Row<VEC, G, CPL>(&xl)[NB], Row<VEC, G, CPL>(&xs)[NB]) {
-    const int64_t row = line_probe_resolve(sd[tA].slots, sd[tA].cap, sd[tA].colbit, kA, svA, lane);
-    const uint32_t s = it * 8 + kq;
-    const bool valid = s < slots;
-    const bool head = j == 0 && valid;
-    const bool missed = head && row < 0;
-    if (a.rows && head && row >= 0) a.rows[a.rrec ? (int64_t)s : (int64_t)tA * B + s / T32] = row;
-    const uint64_t mm = __ballot(missed);
-    if (mm) {
-      const int leader = __ffsll((unsigned long long)mm) - 1;
-      unsigned long long at = 0;
-      if (lane == leader) at = atomicAdd(mcnt, (unsigned long long)__popcll(mm));
-      at = __shfl(at, leader, 64);
-      if (missed) mlist[at + __popcll(mm & lanemask_lt())] = (int32_t)s;
-    }
-    const uint64_t mine = (uint64_t)(uintptr_t)(sd[tA].pool + (row >= 0 ? row : 0) * rstride);
-    const uint64_t okc = __ballot(valid && row >= 0);
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)mine, base + 8 * q, 64);
-      const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(mine >> 32), base + 8 * q, 64);
-      load_row_copy_u<VEC, G, CPL, WIDEN>(
-          xl[q], reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo)), lg, dv);
-    }
-    kA = kB;
-    tA = sB % T32;
-    svA = line_probe_issue(sd[tA].slots, sd[tA].cap, kA, j);
-    sB = slot_of(it + 2 * LW);
-    kB = key_at(sB);
-    store_item(xs);
-    okp = okc;
-    itp = it;
-    it += LW;
-  };
-  for (;;) {
-    step(X0, X1);
-    if (it >= i1) {
-      store_item(X0);
-      break;
-    }
-    step(X1, X0);
-    if (it >= i1) {
-      store_item(X1);
-      break;
-    }
+    int64_t bq;
+    int tq;
+    slot_bt(ws0 + (base / G) * NB + q, T, B, 0, &bq, &tq);
+    float* dst = ((okm >> (base + 8 * q)) & 1ull)
+                     ? a.io.out + bq * a.io.out_stride + (int64_t)tq * dim
+                     : junk + q * 256;
+    store_row_sel<VEC, G, ORDER>(x[q], dst, junk, lg, dv);
   }
 }
 
@@ -2297,9 +2187,9 @@ __global__ __launch_bounds__(256) void ev_miss_kernel(MissArgs a, int T, int64_t
   if (n == 0) return;  // uniform over the grid
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthreads) {
-    const int64_t s = mlist[i];
-    const int64_t b = s / T;
-    const int t = (int)(s - b * T);
+    int64_t b;
+    int t;
+    slot_bt(mlist[i], T, B, 0, &b, &t);
     const EvDesc& e = a.e[t];
     bool created;
     uint64_t rc;
@@ -2335,9 +2225,9 @@ __global__ __launch_bounds__(256) void ev_miss_kernel(MissArgs a, int T, int64_t
   }
   miss_grid_sync(bar, 2 * gridDim.x, st);
   for (int64_t i = w0; i < n; i += waves) {
-    const int64_t s = mlist[i];
-    const int64_t b = s / T;
-    const int t = (int)(s - b * T);
+    int64_t b;
+    int t;
+    slot_bt(mlist[i], T, B, 0, &b, &t);
     const float* src = mrow[i] >= 0 ? a.pool[t] + mrow[i] * dim : a.dflt[t];
     if (a.rows && lane == 0)
       a.rows[a.rrec ? b * T + t : (int64_t)t * B + b] = mrow[i] >= 0 ? mrow[i] : -1;
@@ -2368,7 +2258,7 @@ static unsigned miss_blocks() {
 }
 
 struct LookupWs {
-  float* junk;  // 16 KB sink of the branch-free stores (line / pipe kernels)
+  float* junk;  // 16 KB sink of the branch-free stores (line kernel)
   int32_t* mlist;
   unsigned long long* mcnt;  // [2]: miss count, grid-barrier counter
   int64_t* mrow;
@@ -2387,143 +2277,84 @@ static LookupWs carve_lookup(void* ws, int64_t n, size_t* used) {
   return w;
 }
 
-template <int VEC, int G, int CPL, int ORDER, int NB, bool WIDEN = false>
-static void launch_lookup_nb(const LookupArgs& a, int T, int64_t B, int dim, const LookupWs& w,
-                             hipStream_t st) {
-  const int64_t items = ceil_div((int64_t)T * B, NB);
-  timing_mark(DR_TIME_LOOKUP, st, true);
-  hipLaunchKernelGGL((ev_lookup_onehot_kernel<VEC, G, CPL, ORDER, NB, WIDEN>),
-                     dim3((unsigned)ceil_div(items, 256 / G)), dim3(256), 0, st, a, T, B, dim,
-                     w.mlist, w.mcnt);
-  timing_mark(DR_TIME_LOOKUP, st, false);
-}
-
-// DR_LOOKUP_KERNEL (A/B switch): 0 = slot-by-slot one-shot kernel (NB rows
-// per lane group), 1 = line probes, one-shot (ev_lookup_line_kernel), 2 =
-// line probes, software-pipelined persistent waves (ev_lookup_pipe_kernel).
-static int lookup_kernel_kind() {   // read per launch (host only): tests cover each kernel
-  const char* e = getenv("DR_LOOKUP_KERNEL");
-  return e ? atoi(e) : 1;
-}
-
-// Persistent grid of a 256-thread kernel: resident blocks per CU x CUs,
-// a multiple of 8 (XCD-major item ranges), at most `want`.
-template <class K>
-static unsigned persistent_grid(K kernel, int64_t want) {
-  // resident blocks of this kernel on this device, asked once
-  static std::mutex mu;
-  static std::vector<std::pair<std::pair<const void*, int>, int64_t>> cache;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  const void* key = reinterpret_cast<const void*>(kernel);
-  int64_t g = 0;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : cache)
-      if (e.first.first == key && e.first.second == dev) g = e.second;
-  }
-  if (g == 0) {
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-      cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, 256, 0) != hipSuccess ||
-        per <= 0)
-      per = 1;
-    g = (int64_t)per * cus;
-    std::lock_guard<std::mutex> lk(mu);
-    cache.push_back({{key, dev}, g});
-  }
-  want = ceil_div(want, 8) * 8;
-  if (g > want) g = want;
-  g = std::max<int64_t>(8, g / 8 * 8);
-  return (unsigned)g;
-}
-
-// Line-probe lookups (8 lanes per key: G = 8 NB); false when the shape or
-// the switch leaves it to the slot-by-slot kernel.
-template <int VEC, int G, int CPL, int ORDER, bool WIDEN>
-static bool launch_lookup_line(const LookupArgs& a, int T, int64_t B, int dim, const LookupWs& w,
-                               hipStream_t st) {
-  if constexpr (G % 8 != 0) {
-    return false;
-  } else {
-    const int kind = lookup_kernel_kind();
-    if (kind == 0 || a.tmaj) return false;
-    const int64_t waves = ceil_div((int64_t)T * B, 8);
-    timing_mark(DR_TIME_LOOKUP, st, true);
-    if (kind == 1) {
-      hipLaunchKernelGGL((ev_lookup_line_kernel<VEC, G, CPL, ORDER, WIDEN>),
-                         dim3((unsigned)ceil_div(waves, 4)), dim3(256), 0, st, a, T, B, dim,
-                         w.mlist, w.mcnt, w.junk);
-    } else {
-      const unsigned grid =
-          persistent_grid(ev_lookup_pipe_kernel<VEC, G, CPL, ORDER, WIDEN>, ceil_div(waves, 4));
-      hipLaunchKernelGGL((ev_lookup_pipe_kernel<VEC, G, CPL, ORDER, WIDEN>), dim3(grid), dim3(256),
-                         0, st, a, T, B, dim, w.mlist, w.mcnt, w.junk);
+// One fused lookup launch, chosen by the input alone: line probes (8 lanes
+// per key, G / 8 rows per lane group) in output order for rows of more than
+// 16 words; the slot-by-slot kernel for shorter rows (G = 4) and for table
+// order (DR_LOOKUP_TABLE_ORDER).
+template <int G, int ORDER, bool WIDEN>
+static void launch_lookup(const LookupArgs& a, int T, int64_t B, int dim, const LookupWs& w,
+                          hipStream_t st) {
+  const int64_t n = (int64_t)T * B;
+  if constexpr (G >= 8) {
+    if (!a.io.tmaj) {
+      hipLaunchKernelGGL((ev_lookup_line_kernel<4, G, ORDER, WIDEN>),
+                         dim3((unsigned)ceil_div(ceil_div(n, 8), 4)), dim3(256), 0, st, a, T, B,
+                         dim, w.mlist, w.mcnt, w.junk);
+      return;
     }
-    timing_mark(DR_TIME_LOOKUP, st, false);
-    return true;
   }
-}
-
-template <int VEC, int G, int CPL, int ORDER>
-static void launch_lookup_onehot(const LookupArgs& a, int T, int64_t B, int dim, const LookupWs& w,
-                                 hipStream_t st) {
-  if (launch_lookup_line<VEC, G, CPL, ORDER, false>(a, T, B, dim, w, st)) return;
   // rows in flight per lane group: 2 for rows of <= 64 floats (D = 64:
   // 0.194 against 0.200 ms for 4, profiles/r04_lookup_ab_nb2.log -- more,
   // smaller groups hide the dependent slot probe better), 4 above (D = 128:
-  // the step, not the kernel alone, is 0.7 % slower with 2)
-  static const int nb_env = getenv("DR_LOOKUP_NB") ? atoi(getenv("DR_LOOKUP_NB")) : 0;
-  const int nb = nb_env ? nb_env : (G <= 16 ? 2 : 4);
-  if (nb == 8 && G >= 8)
-    launch_lookup_nb<VEC, G, CPL, ORDER, 8>(a, T, B, dim, w, st);
-  else if (nb == 2)
-    launch_lookup_nb<VEC, G, CPL, ORDER, 2>(a, T, B, dim, w, st);
-  else
-    launch_lookup_nb<VEC, G, CPL, ORDER, 4>(a, T, B, dim, w, st);
+  // the step, not the kernel alone, is 0.7 % slower with 2) and when widening
+  constexpr int NB = (WIDEN || G > 16) ? 4 : 2;
+  hipLaunchKernelGGL((ev_lookup_onehot_kernel<4, G, ORDER, NB, WIDEN>),
+                     dim3((unsigned)ceil_div(ceil_div(n, NB), 256 / G)), dim3(256), 0, st, a, T, B,
+                     dim, w.mlist, w.mcnt);
+}
+
+// The argument checks that the training and the read-only fused lookup share.
+// bf16 EVs (value_bits 16): an fp32 output widens each value (the reference
+// casts bf16 embeddings to float32, embedding_ops.py:606-607); with
+// DR_LOOKUP_OUT_BF16 the rows are copied bitwise as D / 2 float words into a
+// bf16 output.  *out_stride counts elements of the output type on entry and
+// float words on return; *dim: floats per output row segment (and per row,
+// except when widening, where a row is dim / 2 words).
+static int lookup_check(dr_ev* const* evs, int T, int64_t ksb, int64_t kst, int64_t B,
+                        const float* out, int64_t* out_stride, int order, int flags, int64_t* dim,
+                        bool* widen) {
+  DR_REQUIRE(evs && T >= 1 && T <= DR_MAX_GROUP && B >= 0 && *out_stride >= 0,
+             DR_INVALID_ARGUMENT, "bad argument");
+  for (int t = 0; t < T; ++t) DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
+  DR_REQUIRE(ksb >= 0 && kst >= 0, DR_INVALID_ARGUMENT, "key strides must be >= 0");
+  DR_REQUIRE(order == DR_ORDER_ALI || order == DR_ORDER_SEQ, DR_INVALID_ARGUMENT, "bad order");
+  DR_REQUIRE((int64_t)T * B < (1ll << 31), DR_INVALID_ARGUMENT, "T*B must be < 2^31");
+  DR_REQUIRE((flags & ~(DR_LOOKUP_OUT_BF16 | DR_LOOKUP_TABLE_ORDER | DR_LOOKUP_ROWS_RECORD)) == 0,
+             DR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+  const bool bf16 = evs[0]->sh->bf16 && evs[0]->col == 0;
+  const bool out_bf16 = flags & DR_LOOKUP_OUT_BF16;
+  *widen = bf16 && !out_bf16;
+  DR_REQUIRE(!out_bf16 || bf16, DR_INVALID_ARGUMENT, "DR_LOOKUP_OUT_BF16 needs bf16 EVs");
+  DR_REQUIRE(!bf16 || order == DR_ORDER_ALI, DR_INVALID_ARGUMENT,
+             "bf16 EV lookups pool in the ALI order");
+  DR_REQUIRE(!out_bf16 || *out_stride % 2 == 0, DR_INVALID_ARGUMENT,
+             "bf16 output stride must be even");
+  if (out_bf16) *out_stride /= 2;
+  *dim = bf16 && !*widen ? col_words(evs[0]->sh, 0) : evs[0]->sh->dim;
+  DR_REQUIRE(*dim % 4 == 0 && *dim <= 256, DR_INVALID_ARGUMENT,
+             "fused one-hot lookup needs dim %% 4 == 0 (bf16: %% 8) and <= 256 words");
+  DR_REQUIRE(*out_stride >= (int64_t)T * *dim && (*out_stride % 4) == 0 &&
+                 ((uintptr_t)out & 15) == 0,
+             DR_INVALID_ARGUMENT, "out must be 16-B aligned with stride >= T*dim (multiple of 4)");
+  return DR_OK;
 }
 
 static int lookup_onehot(dr_ev* const* evs, int T, const int64_t* keys, int64_t ksb, int64_t kst,
                          int64_t B, float* out, int64_t out_stride, int order, int64_t* rows_out,
                          void* ws, size_t ws_bytes, hipStream_t st, int flags = 0) {
   EvGuard guard_(evs, T);
-  DR_REQUIRE(evs && T >= 1 && T <= DR_MAX_GROUP && B >= 0 && out_stride >= 0, DR_INVALID_ARGUMENT,
-             "bad argument");
-  DR_REQUIRE(ksb >= 0 && kst >= 0, DR_INVALID_ARGUMENT, "key strides must be >= 0");
-  DR_REQUIRE(order == DR_ORDER_ALI || order == DR_ORDER_SEQ, DR_INVALID_ARGUMENT, "bad order");
+  int64_t dim;
+  bool widen;
+  int rc = lookup_check(evs, T, ksb, kst, B, out, &out_stride, order, flags, &dim, &widen);
+  if (rc) return rc;
   const int64_t n = (int64_t)T * B;
-  DR_REQUIRE(n < (1ll << 31), DR_INVALID_ARGUMENT, "T*B must be < 2^31");
   size_t need = 0;
   carve_lookup(nullptr, n, &need);
   DR_REQUIRE(ws_bytes >= need, DR_INVALID_ARGUMENT, "lookup workspace too small");
-  // bf16 EVs (value_bits 16): an fp32 output widens each value (the
-  // reference casts bf16 embeddings to float32, embedding_ops.py:606-607);
-  // with DR_LOOKUP_OUT_BF16 the rows are copied bitwise as D / 2 float words
-  // into a bf16 output.  out_stride counts elements of the output type.
-  DR_REQUIRE((flags & ~(DR_LOOKUP_OUT_BF16 | DR_LOOKUP_TABLE_ORDER | DR_LOOKUP_ROWS_RECORD)) == 0,
-             DR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
-  const bool bf16 = evs[0]->sh->bf16 && evs[0]->col == 0;
-  const bool out_bf16 = flags & DR_LOOKUP_OUT_BF16;
-  const bool widen = bf16 && !out_bf16;
-  DR_REQUIRE(!out_bf16 || bf16, DR_INVALID_ARGUMENT, "DR_LOOKUP_OUT_BF16 needs bf16 EVs");
-  DR_REQUIRE(!bf16 || order == DR_ORDER_ALI, DR_INVALID_ARGUMENT,
-             "bf16 EV lookups pool in the ALI order");
-  DR_REQUIRE(!out_bf16 || out_stride % 2 == 0, DR_INVALID_ARGUMENT,
-             "bf16 output stride must be even");
-  if (out_bf16) out_stride /= 2;                       // float words from here on
-  // floats per output row segment (and per row, except when widening, where
-  // a row is dim / 2 words)
-  const int64_t dim = bf16 && !widen ? col_words(evs[0]->sh, 0) : evs[0]->sh->dim;
-  DR_REQUIRE(dim % 4 == 0 && dim <= 256, DR_INVALID_ARGUMENT,
-             "fused one-hot lookup needs dim %% 4 == 0 (bf16: %% 8) and <= 256 words");
-  DR_REQUIRE(out_stride >= (int64_t)T * dim && (out_stride % 4) == 0 &&
-                 ((uintptr_t)out & 15) == 0,
-             DR_INVALID_ARGUMENT, "out must be 16-B aligned with stride >= T*dim (multiple of 4)");
   if (n == 0) return DR_OK;
   int* stw = status_word();
   DR_REQUIRE(stw, DR_INTERNAL, "status word unavailable");
+  const bool bf16 = evs[0]->sh->bf16 && evs[0]->col == 0;
   for (int t = 0; t < T; ++t) {
     const EvShared* s = evs[t]->sh;
     DR_REQUIRE(s->dim == evs[0]->sh->dim && (s->bf16 && evs[t]->col == 0) == bf16,
@@ -2537,11 +2368,11 @@ static int lookup_onehot(dr_ev* const* evs, int T, const int64_t* keys, int64_t 
   }
   // capacity before any pointer is read (a reserve may grow the tables)
   for (int t = 0; t < T; ++t) {
-    int rc = reserve(evs[t]->sh, B, st);
+    rc = reserve(evs[t]->sh, B, st);
     if (rc) return rc;
   }
   LookupWs w = carve_lookup(ws, n, nullptr);
-  int rc = fill_bytes(w.mcnt, 0, 2 * sizeof(unsigned long long), st);
+  rc = fill_bytes(w.mcnt, 0, 2 * sizeof(unsigned long long), st);
   if (rc) return rc;
   LookupArgs la;
   memset(&la, 0, sizeof(la));
@@ -2549,44 +2380,36 @@ static int lookup_onehot(dr_ev* const* evs, int T, const int64_t* keys, int64_t 
   memset(&ma, 0, sizeof(ma));
   for (int t = 0; t < T; ++t) {
     const EvShared* s = evs[t]->sh;
-    la.d[t].slots = s->slots;
-    la.d[t].cap = s->cap;
-    la.d[t].pool = s->pools[evs[t]->col];
-    la.d[t].colbit = 1ull << (48 + evs[t]->col);
+    la.d[t] = make_lk_desc(evs[t]);
     ma.e[t] = make_desc(evs[t]);
     ma.pool[t] = s->pools[evs[t]->col];
     ma.dflt[t] = s->defaults[evs[t]->col];
   }
-  la.keys = ma.keys = keys;
-  la.ksb = ma.ksb = ksb;
-  la.kst = ma.kst = kst;
-  la.rows = ma.rows = rows_out;
-  la.out = ma.out = out;
-  la.out_stride = ma.out_stride = out_stride;
-  la.tmaj = (flags & DR_LOOKUP_TABLE_ORDER) ? 1 : 0;
-  la.rrec = ma.rrec = (flags & DR_LOOKUP_ROWS_RECORD) ? 1 : 0;
+  la.io = make_lk_io(keys, ksb, kst, out, out_stride, rows_out, flags);
+  ma.keys = keys;
+  ma.ksb = ksb;
+  ma.kst = kst;
+  ma.rows = rows_out;
+  ma.out = out;
+  ma.out_stride = out_stride;
+  ma.rrec = la.io.rrec;
   const int d4 = (int)(dim / 4);
-#define DR_LK(G, C)                                                             \
-  do {                                                                          \
-    if (widen) {                                                                \
-      if (!launch_lookup_line<4, G, C, DR_ORDER_ALI, true>(la, T, B, (int)dim, w, st)) \
-        launch_lookup_nb<4, G, C, DR_ORDER_ALI, 4, true>(la, T, B, (int)dim, w, st); \
-    }                                                                           \
-    else if (order == DR_ORDER_ALI)                                             \
-      launch_lookup_onehot<4, G, C, DR_ORDER_ALI>(la, T, B, (int)dim, w, st);   \
-    else                                                                        \
-      launch_lookup_onehot<4, G, C, DR_ORDER_SEQ>(la, T, B, (int)dim, w, st);   \
+#define DR_LK(G)                                                        \
+  do {                                                                  \
+    if (widen)                                                          \
+      launch_lookup<G, DR_ORDER_ALI, true>(la, T, B, (int)dim, w, st);  \
+    else if (order == DR_ORDER_ALI)                                     \
+      launch_lookup<G, DR_ORDER_ALI, false>(la, T, B, (int)dim, w, st); \
+    else                                                                \
+      launch_lookup<G, DR_ORDER_SEQ, false>(la, T, B, (int)dim, w, st); \
   } while (0)
-  // DR_LOOKUP_SPLIT=2 (A/B switch): half the lanes per row, two float4 per
-  // lane -- twice the rows (and probes) per wave in flight
-  static const int split = getenv("DR_LOOKUP_SPLIT") ? atoi(getenv("DR_LOOKUP_SPLIT")) : 1;
-  if (split == 2 && d4 > 8 && d4 <= 16) DR_LK(8, 2);
-  else if (split == 2 && d4 > 16 && d4 <= 32) DR_LK(16, 2);
-  else if (d4 <= 4) DR_LK(4, 1);
-  else if (d4 <= 8) DR_LK(8, 1);
-  else if (d4 <= 16) DR_LK(16, 1);
-  else if (d4 <= 32) DR_LK(32, 1);
-  else DR_LK(64, 1);
+  timing_mark(DR_TIME_LOOKUP, st, true);
+  if (d4 <= 4) DR_LK(4);
+  else if (d4 <= 8) DR_LK(8);
+  else if (d4 <= 16) DR_LK(16);
+  else if (d4 <= 32) DR_LK(32);
+  else DR_LK(64);
+  timing_mark(DR_TIME_LOOKUP, st, false);
 #undef DR_LK
   // capacity mirrors ride on the miss kernel (as on resolve_grouped's init)
   EvShared* mir[DR_MAX_GROUP];
@@ -2639,11 +2462,7 @@ static int lookup_onehot(dr_ev* const* evs, int T, const int64_t* keys, int64_t 
 // reserve() / mirror, so slots, top, freq, version, the pools and the
 // capacity accounting are what they were.
 // ---------------------------------------------------------------------------
-struct RoDesc {
-  const Slot* slots;
-  int64_t cap;
-  const float* pool;
-  uint64_t colbit;
+struct RoDesc : LkDesc {
   const float* dflt;    // the column's default row
   const int64_t* freq;  // Counter EVs only (else nullptr: no admission test)
   int64_t filter_freq;
@@ -2652,10 +2471,7 @@ struct RoDesc {
 static RoDesc make_ro_desc(const dr_ev* ev) {
   const EvShared* s = ev->sh;
   RoDesc d;
-  d.slots = s->slots;
-  d.cap = s->cap;
-  d.pool = s->pools[ev->col];
-  d.colbit = 1ull << (48 + ev->col);
+  static_cast<LkDesc&>(d) = make_lk_desc(ev);
   d.dflt = s->defaults[ev->col];
   const bool counter = s->filter_freq > 0 && s->k_hash == 0 && s->freq;
   d.freq = counter ? s->freq : nullptr;
@@ -2672,12 +2488,7 @@ static_assert(sizeof(RoGroup) + 64 <= 4096, "find kernel arguments exceed 4 KiB"
 
 // Row of `key` when it is to be served (rules 1-3), else -1.
 __device__ __forceinline__ int64_t ro_row(const RoDesc& e, uint64_t key) {
-  LkDesc lk;
-  lk.slots = e.slots;
-  lk.cap = e.cap;
-  lk.pool = e.pool;
-  lk.colbit = e.colbit;
-  int64_t row = ev_probe_row(lk, key);
+  int64_t row = ev_probe_row(e, key);
   if (row >= 0 && e.freq && gld(e.freq + row) < e.filter_freq) row = -1;
   return row;
 }
@@ -2722,24 +2533,9 @@ __global__ __launch_bounds__(256) void ev_gather_ro_kernel(
 
 struct RoLookupArgs {
   RoDesc d[DR_MAX_GROUP];
-  const int64_t* keys;  // id of (bag b, table t) = keys[b * ksb + t * kst]
-  int64_t ksb, kst;
-  float* out;
-  int64_t out_stride;
-  int64_t* rows;  // row served per id (-1: default), or nullptr
-  int tmaj;       // visit slots table by table (s = t * B + b)
-  int rrec;       // rows record-major: rows[b * T + t]
+  LkIo io;
 };
 static_assert(sizeof(RoLookupArgs) + 64 <= 4096, "lookup kernel arguments exceed 4 KiB");
-
-// Slot s -> (bag, table) in the visiting order (T * B < 2^31: host check).
-__device__ __forceinline__ void ro_slot_bt(int64_t s, int T, int64_t B, int tmaj, int64_t* b,
-                                           int* t) {
-  const uint32_t dv = tmaj ? (uint32_t)B : (uint32_t)T;
-  const uint32_t q = (uint32_t)s / dv, r = (uint32_t)s - q * dv;
-  *b = tmaj ? (int64_t)r : (int64_t)q;
-  *t = tmaj ? (int)q : (int)r;
-}
 
 // Fused one-hot read-only lookup: the 8-lanes-per-key home-line probe of
 // ev_lookup_line_kernel, then the row copy -- and nothing else.  A key that
@@ -2762,10 +2558,10 @@ __global__ __launch_bounds__(256) void ev_lookup_ro_kernel(RoLookupArgs a, int T
   const bool valid = s < slots;
   int64_t b;
   int t;
-  ro_slot_bt(valid ? s : slots - 1, T, B, a.tmaj, &b, &t);
+  slot_bt(valid ? s : slots - 1, T, B, a.io.tmaj, &b, &t);
   // the id's round trip overlaps the descriptor staging (ids read once)
   const uint64_t key =
-      (uint64_t)__builtin_nontemporal_load(gp(a.keys + b * a.ksb + (int64_t)t * a.kst));
+      (uint64_t)__builtin_nontemporal_load(gp(a.io.keys + b * a.io.ksb + (int64_t)t * a.io.kst));
   if (threadIdx.x < T) sd[threadIdx.x] = a.d[threadIdx.x];
   __syncthreads();
   if (ws0 >= slots) return;  // whole waves
@@ -2776,8 +2572,8 @@ __global__ __launch_bounds__(256) void ev_lookup_ro_kernel(RoLookupArgs a, int T
   // Counter admission: uniform per table, filter-free tables skip it
   const int64_t* fq = sd[t].freq;
   if (fq && row >= 0 && gld(fq + row) < sd[t].filter_freq) row = -1;
-  if ((lane & 7) == 0 && valid && a.rows)
-    a.rows[a.rrec ? b * T + t : (int64_t)t * B + b] = row;
+  if ((lane & 7) == 0 && valid && a.io.rows)
+    a.io.rows[a.io.rrec ? b * T + t : (int64_t)t * B + b] = row;
   const int64_t rstride = WIDEN ? dim / 2 : dim;
   const uint64_t mine =
       (uint64_t)(uintptr_t)(row >= 0 ? sd[t].pool + row * rstride : sd[t].dflt);
@@ -2785,14 +2581,10 @@ __global__ __launch_bounds__(256) void ev_lookup_ro_kernel(RoLookupArgs a, int T
   const int dv = dim / VEC;
   const float* p[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)mine, base + 8 * q, 64);
-    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(mine >> 32), base + 8 * q, 64);
-    p[q] = reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo));
-  }
+  for (int q = 0; q < NB; ++q) p[q] = bcast_row_ptr(mine, base + 8 * q);
   Row<VEC, G, 1> x[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) load_row_copy_u<VEC, G, 1, WIDEN>(x[q], p[q], lg, dv);
+  for (int q = 0; q < NB; ++q) load_row_copy_u<VEC, G, WIDEN>(x[q], p[q], lg, dv);
   const int col = lg < dv ? lg : dv - 1;
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
@@ -2800,10 +2592,10 @@ __global__ __launch_bounds__(256) void ev_lookup_ro_kernel(RoLookupArgs a, int T
     sq = sq < slots ? sq : slots - 1;
     int64_t bq;
     int tq;
-    ro_slot_bt(sq, T, B, a.tmaj, &bq, &tq);
+    slot_bt(sq, T, B, a.io.tmaj, &bq, &tq);
     if (ORDER == DR_ORDER_SEQ)  // fused op: out = 0 + e (-0.0 -> +0.0)
       x[q].v[0] = vadd(vzero<typename VecT<VEC>::T>(), x[q].v[0]);
-    float* dst = a.out + bq * a.out_stride + (int64_t)tq * dim + (int64_t)col * VEC;
+    float* dst = a.io.out + bq * a.io.out_stride + (int64_t)tq * dim + (int64_t)col * VEC;
     nt_store(x[q].v[0], reinterpret_cast<typename VecT<VEC>::T*>(dst));
   }
 }
@@ -2846,35 +2638,15 @@ static int find_grouped(dr_ev* const* evs, int T, const int64_t* keys, const int
 static int lookup_onehot_readonly(dr_ev* const* evs, int T, const int64_t* keys, int64_t ksb,
                                   int64_t kst, int64_t B, float* out, int64_t out_stride,
                                   int order, int flags, int64_t* rows_out, hipStream_t st) {
-  DR_REQUIRE(evs && T >= 1 && T <= DR_MAX_GROUP && B >= 0 && out_stride >= 0, DR_INVALID_ARGUMENT,
-             "bad argument");
-  for (int t = 0; t < T; ++t) DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
-  DR_REQUIRE(ksb >= 0 && kst >= 0, DR_INVALID_ARGUMENT, "key strides must be >= 0");
-  DR_REQUIRE(order == DR_ORDER_ALI || order == DR_ORDER_SEQ, DR_INVALID_ARGUMENT, "bad order");
-  const int64_t n = (int64_t)T * B;
-  DR_REQUIRE(n < (1ll << 31), DR_INVALID_ARGUMENT, "T*B must be < 2^31");
-  DR_REQUIRE(n == 0 || (keys && out), DR_INVALID_ARGUMENT, "null keys / out");
-  DR_REQUIRE((flags & ~(DR_LOOKUP_OUT_BF16 | DR_LOOKUP_TABLE_ORDER | DR_LOOKUP_ROWS_RECORD)) == 0,
-             DR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
   EvGuard guard_(evs, T);
-  // value types as in lookup_onehot: bf16 rows widened into an fp32 output,
-  // or (DR_LOOKUP_OUT_BF16) copied bitwise as D / 2 float words
-  const bool bf16 = evs[0]->sh->bf16 && evs[0]->col == 0;
-  const bool out_bf16 = flags & DR_LOOKUP_OUT_BF16;
-  const bool widen = bf16 && !out_bf16;
-  DR_REQUIRE(!out_bf16 || bf16, DR_INVALID_ARGUMENT, "DR_LOOKUP_OUT_BF16 needs bf16 EVs");
-  DR_REQUIRE(!bf16 || order == DR_ORDER_ALI, DR_INVALID_ARGUMENT,
-             "bf16 EV lookups pool in the ALI order");
-  DR_REQUIRE(!out_bf16 || out_stride % 2 == 0, DR_INVALID_ARGUMENT,
-             "bf16 output stride must be even");
-  if (out_bf16) out_stride /= 2;  // float words from here on
-  const int64_t dim = bf16 && !widen ? col_words(evs[0]->sh, 0) : evs[0]->sh->dim;
-  DR_REQUIRE(dim % 4 == 0 && dim <= 256, DR_INVALID_ARGUMENT,
-             "fused one-hot lookup needs dim %% 4 == 0 (bf16: %% 8) and <= 256 words");
-  DR_REQUIRE(out_stride >= (int64_t)T * dim && (out_stride % 4) == 0 &&
-                 ((uintptr_t)out & 15) == 0,
-             DR_INVALID_ARGUMENT, "out must be 16-B aligned with stride >= T*dim (multiple of 4)");
+  int64_t dim;
+  bool widen;
+  const int rc = lookup_check(evs, T, ksb, kst, B, out, &out_stride, order, flags, &dim, &widen);
+  if (rc) return rc;
+  const int64_t n = (int64_t)T * B;
+  DR_REQUIRE(n == 0 || (keys && out), DR_INVALID_ARGUMENT, "null keys / out");
   if (n == 0) return DR_OK;
+  const bool bf16 = evs[0]->sh->bf16 && evs[0]->col == 0;
   RoLookupArgs la;
   memset(&la, 0, sizeof(la));
   for (int t = 0; t < T; ++t) {
@@ -2888,14 +2660,7 @@ static int lookup_onehot_readonly(dr_ev* const* evs, int T, const int64_t* keys,
                DR_INVALID_ARGUMENT, "pool alignment");
     la.d[t] = make_ro_desc(evs[t]);
   }
-  la.keys = keys;
-  la.ksb = ksb;
-  la.kst = kst;
-  la.rows = rows_out;
-  la.out = out;
-  la.out_stride = out_stride;
-  la.tmaj = (flags & DR_LOOKUP_TABLE_ORDER) ? 1 : 0;
-  la.rrec = (flags & DR_LOOKUP_ROWS_RECORD) ? 1 : 0;
+  la.io = make_lk_io(keys, ksb, kst, out, out_stride, rows_out, flags);
   const int d4 = (int)(dim / 4);
 #define DR_RO(G)                                                              \
   do {                                                                        \

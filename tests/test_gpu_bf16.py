@@ -86,11 +86,12 @@ def test_bf16_synthetic_rows(dr, orc):
 
 
 @pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("D", [16, 64, 128])
 def test_bf16_onehot_lookup(dr, orc, D, out_dtype):
     """Forward-only fused one-hot lookup (dr_ev_lookup_onehot_ex): the bf16
     rows widened into an fp32 output, or copied bitwise into a bf16 output;
-    misses created with the (rounded) default."""
+    misses created with the (rounded) default.  D = 16 is the slot walk (rows
+    of <= 16 words), the others the line kernel."""
     rng = np.random.default_rng(D)
     F, B = 5, 700
     evs, oevs = [], []

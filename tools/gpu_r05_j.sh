@@ -1,5 +1,5 @@
-# Round 5, batch J: every lookup kernel and every long-run walker through
-# the parity tests (per-call DR_LOOKUP_KERNEL / DR_GRAD_SERIAL_PLAIN), then
+# Round 5, batch J: the lookup kernels and every long-run walker through
+# the parity tests (per-call DR_GRAD_SERIAL_PLAIN), then
 # the headline parity at full size.  Tag $1.
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
