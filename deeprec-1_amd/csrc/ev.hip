@@ -2509,6 +2509,25 @@ __global__ void ev_find_kernel(RoGroup g, int T, const int64_t* __restrict__ key
   rows_out[i] = row >= 0 ? row : -(li + 1);
 }
 
+// The row `key` is served from: its stored row (rules 1-3), else the
+// table's default row.  `words`: float words per row.
+__device__ __forceinline__ const float* ro_src(const RoDesc& e, uint64_t key, int64_t words) {
+  const int64_t row = ro_row(e, key);
+  return row >= 0 ? e.pool + row * words : e.dflt;
+}
+
+// Lane lg of the G lanes of a row copies its share (vec: 16-B chunks).
+template <int G>
+__device__ __forceinline__ void ro_copy_row(const float* __restrict__ src, float* __restrict__ dst,
+                                            int64_t words, int vec, int lg) {
+  if (vec) {
+    for (int64_t c = lg; c < words / 4; c += G)
+      reinterpret_cast<float4*>(dst)[c] = gld(reinterpret_cast<const float4*>(src) + c);
+  } else {
+    for (int64_t c = lg; c < words; c += G) dst[c] = gld(src + c);
+  }
+}
+
 // Read-only gather, G lanes per key: out[i] = the key's row, defaults[i]
 // (nullable) or the column's default row.  The G lanes probe together (the
 // same addresses: one request), so there is no row-index array in between.
@@ -2522,13 +2541,32 @@ __global__ __launch_bounds__(256) void ev_gather_ro_kernel(
   const int lg = threadIdx.x % G;
   const int64_t row = ro_row(e, (uint64_t)keys[i]);
   const float* src = row >= 0 ? e.pool + row * words : (defaults ? defaults + i * words : e.dflt);
-  float* dst = out + i * words;
-  if (vec) {
-    for (int64_t c = lg; c < words / 4; c += G)
-      reinterpret_cast<float4*>(dst)[c] = gld(reinterpret_cast<const float4*>(src) + c);
-  } else {
-    for (int64_t c = lg; c < words; c += G) dst[c] = gld(src + c);
-  }
+  ro_copy_row<G>(src, out + i * words, words, vec, lg);
+}
+
+// Owner side of the sharded engines' read-only forward: per-entry table
+// index, so the descriptors are staged in LDS (the RoGroup idiom).
+struct RoTables {
+  RoDesc d[DR_MAX_GROUP];
+};
+static_assert(sizeof(RoTables) + 128 <= 4096, "read-only owner kernel arguments exceed 4 KiB");
+
+// Read-only owner-side pack of the all-to-all engines (the counterpart of
+// dr_ev_resolve_tagged + ev_gather_tagged_kernel): out[i] = the served row of
+// keys[i] in table tags[i], or that table's default row.  G lanes per key
+// probe together (one request) and copy; no row-index array, no workspace.
+template <int G>
+__global__ __launch_bounds__(256) void ev_gather_ro_tagged_kernel(
+    RoTables g, int T, int64_t words, int vec, const int64_t* __restrict__ keys,
+    const int32_t* __restrict__ tags, int64_t n, const int64_t* n_dev, float* __restrict__ out) {
+  __shared__ RoDesc sd[DR_MAX_GROUP];
+  if (threadIdx.x < T) sd[threadIdx.x] = g.d[threadIdx.x];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  if (i >= eff_n(n, n_dev)) return;
+  const int t = tags[i];   // (a tag outside [0, T) reads table 0, never past the staged array)
+  const float* src = ro_src(sd[(unsigned)t < (unsigned)T ? t : 0], (uint64_t)keys[i], words);
+  ro_copy_row<G>(src, out + i * words, words, vec, threadIdx.x % G);
 }
 
 struct RoLookupArgs {
@@ -3101,6 +3139,45 @@ int dr_ev_gather_readonly(dr_ev* ev, const int64_t* keys, int64_t n, const void*
   return DR_OK;
 }
 
+int dr_ev_gather_tagged_readonly(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                                 const int32_t* tags, int64_t n, const int64_t* n_dev, void* out,
+                                 void* stream) {
+  using namespace dr;
+  DR_REQUIRE(evs && num_tables >= 1 && num_tables <= DR_MAX_GROUP && n >= 0, DR_INVALID_ARGUMENT,
+             "bad argument");
+  DR_REQUIRE(n == 0 || (keys && tags && out), DR_INVALID_ARGUMENT, "null keys / tags / out");
+  for (int t = 0; t < num_tables; ++t) DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
+  EvGuard guard_(evs, num_tables);
+  if (n == 0) return DR_OK;
+  RoTables g;
+  memset(&g, 0, sizeof(g));
+  const EvShared* s0 = evs[0]->sh;
+  const int64_t words = col_words(s0, evs[0]->col);
+  const bool bf16 = s0->bf16 && evs[0]->col == 0;
+  uintptr_t align = (uintptr_t)out;
+  for (int t = 0; t < num_tables; ++t) {
+    const EvShared* s = evs[t]->sh;
+    DR_REQUIRE(col_words(s, evs[t]->col) == words && s->value_words == s0->value_words &&
+                   (s->bf16 && evs[t]->col == 0) == bf16,
+               DR_INVALID_ARGUMENT, "tables must share row words and value type");
+    g.d[t] = make_ro_desc(evs[t]);
+    align |= (uintptr_t)g.d[t].pool | (uintptr_t)g.d[t].dflt;
+  }
+  const int vec = words % 4 == 0 && (align & 15) == 0;
+  hipStream_t st = S(stream);
+  // 8 lanes per key at every row width (a lane copies every 8th chunk): the
+  // probe is a dependent chain, and 8 keys a wave keep 4x the probes in
+  // flight of one 16-B chunk per lane on 128-word rows.  Measured on the
+  // fixed kind (26 x 65536 keys, 128-word rows): 1.10 ms a forward with 8 or
+  // 16 lanes per key, 1.25 ms with 32.
+  constexpr int G = 8;
+  hipLaunchKernelGGL(ev_gather_ro_tagged_kernel<G>, dim3((unsigned)ceil_div(n, 256 / G)),
+                     dim3(256), 0, st, g, num_tables, words, vec, keys, tags, n, n_dev,
+                     static_cast<float*>(out));
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
 int dr_ev_lookup_onehot_readonly(dr_ev* const* evs, int num_tables, const int64_t* keys,
                                  int64_t key_stride_bag, int64_t key_stride_table,
                                  int64_t batch, void* out, int64_t out_stride, int order,
@@ -3565,6 +3642,8 @@ int dr_ev_apply_adam(dr_ev* var, dr_ev* m, dr_ev* v, float beta1_power, float be
 //   init   : first-touch default rows (kernel boundary: before any read)
 //   emit   : row -> out[src][slot * dim] of the requester, over xGMI
 //            (1-D grid, destinations interleaved block by block)
+// dr_xgmi_serve_readonly (evaluation / serving) is one launch instead: the
+// emit with the read-only probe in place of the resolve's row array.
 // ===========================================================================
 namespace dr {
 
@@ -3705,6 +3784,73 @@ __global__ __launch_bounds__(256) void xgmi_emit_kernel(XgmiRowArgs a,
         const float* row = r >= 0 ? spool[t] + r * a.dim : sdflt[t];
         x[k] = __builtin_nontemporal_load(reinterpret_cast<const xf4*>(row) + lg);
         dst[k] = out + (int64_t)sl * a.dim;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+      if (dst[k]) __builtin_nontemporal_store(x[k], reinterpret_cast<xf4*>(dst[k]) + lg);
+  }
+  // no per-block system fence here: xgmi_flush_kernel follows the launch
+}
+
+// Read-only owner side (dr_xgmi_serve_readonly): resolve, init and emit in
+// one launch over no workspace.  The structure is xgmi_emit_kernel's; the
+// row address comes from the read-only probe (ro_src: rules 1-3 of the
+// RoDesc comment, else the table's default row) where the emit reads the
+// resolve's row array.  Lane k < NB of a group probes entry i0 + k -- the NB
+// probes of a group, then its NB rows, are in flight together -- and the
+// group takes each row address from that lane.
+struct XgmiRoArgs {
+  RoTables g;
+  float* out[DR_MAX_PEERS];
+  const int64_t* keys;  // local inbox [world][cap]
+  const int32_t* slot;
+  const int64_t* cnt;
+  int64_t cap;
+  int64_t dim;
+  int T;
+  int world;
+};
+static_assert(sizeof(XgmiRoArgs) + 64 <= 4096, "read-only serve kernel arguments exceed 4 KiB");
+
+template <int G, int NB>
+__global__ __launch_bounds__(256) void xgmi_serve_ro_kernel(XgmiRoArgs a) {
+  static_assert(NB <= G, "one probing lane per row in flight");
+  __shared__ RoDesc sd[DR_MAX_GROUP];  // per-lane table index: stage in LDS
+  if (threadIdx.x < a.T) sd[threadIdx.x] = a.g.d[threadIdx.x];
+  __syncthreads();
+  // destinations interleaved block by block, as in xgmi_emit_kernel
+  const int W = a.world;
+  const int src = (int)(blockIdx.x % (unsigned)W);
+  const int64_t bx = blockIdx.x / (unsigned)W;
+  const int64_t nbx = gridDim.x / (unsigned)W;
+  const int64_t n = inbox_count(a.cnt, src);
+  constexpr int GPB = 256 / G;
+  const int lane = (int)(threadIdx.x & 63);
+  const int lg = threadIdx.x % G, base = lane - lg;
+  const int dv = (int)(a.dim / 4);
+  const int64_t grp = bx * GPB + threadIdx.x / G;
+  const int64_t ngrp = nbx * GPB;
+  float* out = a.out[src];
+  for (int64_t i0 = grp * NB; i0 < n; i0 += ngrp * NB) {
+    uint64_t mine = 0;   // (0: no entry)
+    int32_t sl = 0;
+    if (lg < NB && i0 + lg < n) {
+      const int64_t j = (int64_t)src * a.cap + i0 + lg;
+      sl = a.slot[j];
+      mine = (uint64_t)(uintptr_t)ro_src(sd[sl % a.T], (uint64_t)a.keys[j], a.dim);
+    }
+    xf4 x[NB];
+    float* dst[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      const float* row = bcast_row_ptr(mine, base + k);
+      const int32_t sk = __shfl(sl, base + k, 64);
+      dst[k] = nullptr;
+      x[k] = xf4{0.f, 0.f, 0.f, 0.f};
+      if (row && lg < dv) {
+        x[k] = __builtin_nontemporal_load(reinterpret_cast<const xf4*>(row) + lg);
+        dst[k] = out + (int64_t)sk * a.dim;
       }
     }
 #pragma unroll
@@ -3855,6 +4001,67 @@ int dr_xgmi_serve(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
     hipLaunchKernelGGL((xgmi_emit_kernel<64, 4>), ge(64), dim3(256), 0, st, wa, w.rows);
   // (one rank: the rows stay on this device, whose next kernels see them
   // after the kernel boundary -- no system-scope release needed)
+  if (W > 1) hipLaunchKernelGGL(xgmi_flush_kernel, dim3(64), dim3(64), 0, st);
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+// The owner side without insert-on-miss (EmbeddingVar::Lookup semantics, see
+// RoDesc): one launch, no workspace, no reserve() and no counter mirror.
+// Counter / Bloom filter EVs are accepted -- admission is one dependent load.
+int dr_xgmi_serve_readonly(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
+                           int64_t batch, void* stream) {
+  using namespace dr;
+  DR_REQUIRE(peers && evs && num_tables >= 1 && num_tables <= DR_MAX_GROUP && batch >= 0,
+             DR_INVALID_ARGUMENT, "bad argument");
+  for (int t = 0; t < num_tables; ++t) DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
+  EvGuard guard_(evs, num_tables);
+  const int W = peers->world;
+  const int r = peers->rank;
+  DR_REQUIRE(W >= 1 && W <= DR_MAX_PEERS && r >= 0 && r < W && peers->cap > 0,
+             DR_INVALID_ARGUMENT, "bad world/rank/cap");
+  const int64_t dim = col_words(evs[0]->sh, evs[0]->col);
+  DR_REQUIRE(dim % 4 == 0 && dim <= 256, DR_INVALID_ARGUMENT,
+             "xgmi serve needs row words %% 4 == 0 and <= 256 (got %lld)", (long long)dim);
+  XgmiRoArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int t = 0; t < num_tables; ++t) {
+    const EvShared* s = evs[t]->sh;
+    DR_REQUIRE(col_words(s, evs[t]->col) == dim && s->bf16 == evs[0]->sh->bf16,
+               DR_INVALID_ARGUMENT, "tables must share dim and value type");
+    DR_REQUIRE(s->value_words == 1, DR_INVALID_ARGUMENT,
+               "table %d: xgmi serve is for fp32 / bf16 EVs", t);
+    a.g.d[t] = make_ro_desc(evs[t]);
+    DR_REQUIRE((((uintptr_t)a.g.d[t].pool | (uintptr_t)a.g.d[t].dflt) & 15) == 0,
+               DR_INVALID_ARGUMENT, "pool alignment");
+  }
+  DR_REQUIRE(peers->inbox_keys[r] && peers->inbox_slot[r] && peers->inbox_cnt[r],
+             DR_INVALID_ARGUMENT, "own inbox not set");
+  for (int p = 0; p < W; ++p) {
+    DR_REQUIRE(peers->out[p], DR_INVALID_ARGUMENT, "peer %d output not mapped", p);
+    a.out[p] = peers->out[p];
+  }
+  a.keys = peers->inbox_keys[r];
+  a.slot = peers->inbox_slot[r];
+  a.cnt = peers->inbox_cnt[r];
+  a.cap = peers->cap;
+  a.dim = dim;
+  a.T = num_tables;
+  a.world = W;
+  hipStream_t st = S(stream);
+  // the emit's one-shot grid (see dr_xgmi_serve)
+  const int64_t per_src = std::max<int64_t>(1, (int64_t)num_tables * batch / W);
+  const int64_t expect = per_src + per_src / 4 + 256;
+  const int dv = (int)(dim / 4);
+  auto ge = [&](int G) { return dim3((unsigned)(ceil_div(expect, (256 / G) * 4) * W)); };
+  if (dv <= 8)
+    hipLaunchKernelGGL((xgmi_serve_ro_kernel<8, 4>), ge(8), dim3(256), 0, st, a);
+  else if (dv <= 16)
+    hipLaunchKernelGGL((xgmi_serve_ro_kernel<16, 4>), ge(16), dim3(256), 0, st, a);
+  else if (dv <= 32)
+    hipLaunchKernelGGL((xgmi_serve_ro_kernel<32, 4>), ge(32), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((xgmi_serve_ro_kernel<64, 4>), ge(64), dim3(256), 0, st, a);
   if (W > 1) hipLaunchKernelGGL(xgmi_flush_kernel, dim3(64), dim3(64), 0, st);
   DR_LAUNCH_CHECK();
   return DR_OK;

@@ -595,7 +595,10 @@ static int xgmi_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_h
   hipStream_t st = S(stream);
   int rc = dr_xgmi_route_ex(&s->peers, ids, T, B, nullptr, s->xcnt.as<int64_t>(), stream);
   if (!rc) rc = comm_barrier(s->comm, st);
-  if (!rc) rc = dr_xgmi_serve(&s->peers, s->evs.data(), T, B, s->xws.p, s->xws.bytes, stream);
+  if (!rc)
+    rc = (flags & DR_SHARDED_READ_ONLY)
+             ? dr_xgmi_serve_readonly(&s->peers, s->evs.data(), T, B, stream)
+             : dr_xgmi_serve(&s->peers, s->evs.data(), T, B, s->xws.p, s->xws.bytes, stream);
   if (!rc) rc = comm_barrier(s->comm, st);
   if (rc) return rc;
   s->saved = need_grad != 0;
@@ -667,15 +670,19 @@ static int fixed_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_
   DR_ENS(s->kr, GC * 8);
   DR_ENS(s->tr, GC * 4);
   DR_ENS(s->hr, (size_t)GT * 8);
-  DR_ENS(s->kc, GC * 8);
-  DR_ENS(s->tc, GC * 4);
-  DR_ENS(s->rtot, 8);
-  DR_ENS(s->rows_c, GC * 8);
-  DR_ENS(s->rows_f, GC * 8);
-  DR_ENS(s->tags_f, GC * 4);
+  const bool read_only = (flags & DR_SHARDED_READ_ONLY) != 0;
+  if (!read_only) {   // (the read-only owner has no compacted keys and no row arrays)
+    DR_ENS(s->kc, GC * 8);
+    DR_ENS(s->tc, GC * 4);
+    DR_ENS(s->rtot, 8);
+    DR_ENS(s->rows_c, GC * 8);
+    DR_ENS(s->rows_f, GC * 8);
+    DR_ENS(s->tags_f, GC * 4);
+  }
   DR_ENS(s->rows_s, GC * vrow);
   DR_ENS(s->rows_r, GC * vrow);
-  size_t wsb = std::max(dr_route_workspace_size(n, G, T), dr_ev_resolve_workspace_size(GC));
+  size_t wsb = dr_route_workspace_size(n, G, T);
+  if (!read_only) wsb = std::max(wsb, dr_ev_resolve_workspace_size(GC));
   if (!direct) {
     wsb = std::max(wsb, dr_unique_grouped_workspace_size(koff.data(), T));
     DR_ENS(s->uniq, nn * 8);
@@ -709,23 +716,33 @@ static int fixed_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_
   if (!rc) rc = a2a_v(s->comm, s->kf.p, hC.data(), s->kr.p, hC.data(), 8, st);
   if (!rc) rc = a2a_v(s->comm, s->tf.p, hC.data(), s->tr.p, hC.data(), 4, st);
   if (rc) return rc;
-  // owner: compact, resolve (device count), rows back into region layout
-  hipLaunchKernelGGL(fx_compact_kernel, dim3((unsigned)ceil_div(GC, 256)), dim3(256), 0, st,
-                     s->kr.as<int64_t>(), s->tr.as<int32_t>(), s->hr.as<int64_t>(), G, T, cap,
-                     s->kc.as<int64_t>(), s->tc.as<int32_t>(), s->rtot.as<int64_t>());
-  DR_LAUNCH_CHECK();
-  // capacity accounting: at most G * max_ids keys of a table arrive per step
-  std::vector<int64_t> per_table(T, (int64_t)G * s->max_ids);
-  rc = dr_ev_resolve_tagged(s->evs.data(), T, s->kc.as<int64_t>(), s->tc.as<int32_t>(), GC,
-                            s->rtot.as<int64_t>(), per_table.data(), nullptr,
-                            s->rows_c.as<int64_t>(), s->ws.p, s->ws.bytes, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(fx_expand_kernel, dim3((unsigned)ceil_div(GC, 256)), dim3(256), 0, st,
-                     s->rows_c.as<int64_t>(), s->tr.as<int32_t>(), s->hr.as<int64_t>(), G, T, cap,
-                     s->rows_f.as<int64_t>(), s->tags_f.as<int32_t>());
-  DR_LAUNCH_CHECK();
-  rc = dr_ev_gather_tagged(s->evs.data(), T, s->tags_f.as<int32_t>(), s->rows_f.as<int64_t>(), GC,
-                           nullptr, s->rows_s.as<float>(), stream);
+  if (read_only) {
+    // Read-only owner: one probe-and-copy launch straight over the received
+    // regions -- no compact, resolve or expand.  A region's padding entries
+    // are key 0 / table 0 (fx_pack_kernel): probing them read-only changes
+    // nothing, and the requester never reads those rows (fx_rowsel_kernel
+    // addresses the counted entries only).
+    rc = dr_ev_gather_tagged_readonly(s->evs.data(), T, s->kr.as<int64_t>(), s->tr.as<int32_t>(),
+                                      GC, nullptr, s->rows_s.p, stream);
+  } else {
+    // owner: compact, resolve (device count), rows back into region layout
+    hipLaunchKernelGGL(fx_compact_kernel, dim3((unsigned)ceil_div(GC, 256)), dim3(256), 0, st,
+                       s->kr.as<int64_t>(), s->tr.as<int32_t>(), s->hr.as<int64_t>(), G, T, cap,
+                       s->kc.as<int64_t>(), s->tc.as<int32_t>(), s->rtot.as<int64_t>());
+    DR_LAUNCH_CHECK();
+    // capacity accounting: at most G * max_ids keys of a table arrive per step
+    std::vector<int64_t> per_table(T, (int64_t)G * s->max_ids);
+    rc = dr_ev_resolve_tagged(s->evs.data(), T, s->kc.as<int64_t>(), s->tc.as<int32_t>(), GC,
+                              s->rtot.as<int64_t>(), per_table.data(), nullptr,
+                              s->rows_c.as<int64_t>(), s->ws.p, s->ws.bytes, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fx_expand_kernel, dim3((unsigned)ceil_div(GC, 256)), dim3(256), 0, st,
+                       s->rows_c.as<int64_t>(), s->tr.as<int32_t>(), s->hr.as<int64_t>(), G, T, cap,
+                       s->rows_f.as<int64_t>(), s->tags_f.as<int32_t>());
+    DR_LAUNCH_CHECK();
+    rc = dr_ev_gather_tagged(s->evs.data(), T, s->tags_f.as<int32_t>(), s->rows_f.as<int64_t>(), GC,
+                             nullptr, s->rows_s.as<float>(), stream);
+  }
   if (!rc) rc = a2a_v(s->comm, s->rows_s.p, hC.data(), s->rows_r.p, hC.data(), (int64_t)vrow, st);
   if (rc) return rc;
   // requester: pool straight from the received regions
@@ -1071,6 +1088,8 @@ int dr_sharded_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_ho
              "combiner must be sum, mean or sqrtn");
   DR_REQUIRE(!(flags & DR_SHARDED_OUT_BF16) || s->bf16, DR_INVALID_ARGUMENT,
              "a bf16 output needs bf16 EVs");
+  DR_REQUIRE(!(flags & DR_SHARDED_READ_ONLY) || !need_grad, DR_INVALID_ARGUMENT,
+             "a read-only forward keeps no state for a backward (need_grad must be 0)");
   // (XGMI: out may be NULL -- the result stays in the engine buffer)
   if (s->kind == DR_SHARDED_XGMI)
     return xgmi_forward(s, ids, koff_host, bag_off, bags, combiner, need_grad, flags, out, stream);
@@ -1092,6 +1111,7 @@ int dr_sharded_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_ho
   DR_REQUIRE(ids || n == 0, DR_INVALID_ARGUMENT, "null ids");
   hipStream_t st = S(stream);
   s->saved = false;
+  const bool read_only = (flags & DR_SHARDED_READ_ONLY) != 0;
   const bool direct = !need_grad && !bag_off;
   const int64_t nn = n > 0 ? n : 1;
   const size_t vrow = (size_t)D * (s->bf16 ? 2 : 4);   // bytes of one exchanged row
@@ -1151,11 +1171,13 @@ int dr_sharded_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_ho
   const int64_t RR = R > 0 ? R : 1, SS = S > 0 ? S : 1;
   DR_ENS(s->keys_r, RR * 8);
   DR_ENS(s->tags_r, RR * 4);
-  DR_ENS(s->rows, RR * 8);
   DR_ENS(s->rows_s, (size_t)RR * vrow);
   DR_ENS(s->rows_r, (size_t)SS * vrow);
-  const size_t rws = dr_ev_resolve_workspace_size(RR);
-  if (rws > s->ws.bytes) DR_ENS(s->ws, rws);
+  if (!read_only) {   // (the read-only owner has no row array and no resolve workspace)
+    DR_ENS(s->rows, RR * 8);
+    const size_t rws = dr_ev_resolve_workspace_size(RR);
+    if (rws > s->ws.bytes) DR_ENS(s->ws, rws);
+  }
   // 4. keys to the owners
   rc = a2a_v(s->comm, s->keys_s.p, send.data(), s->keys_r.p, recv.data(), 8, st);
   if (rc) return rc;
@@ -1166,13 +1188,19 @@ int dr_sharded_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_ho
     hipLaunchKernelGGL(sh_tags_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, st,
                        s->blk.as<int64_t>(), GT, T, R, s->tags_r.as<int32_t>());
     DR_LAUNCH_CHECK();
-    rc = dr_ev_resolve_tagged(s->evs.data(), T, s->keys_r.as<int64_t>(), s->tags_r.as<int32_t>(),
-                              R, nullptr, per_table.data(), nullptr, s->rows.as<int64_t>(),
-                              s->ws.p, s->ws.bytes, stream);
-    if (rc) return rc;
-    rc = dr_ev_gather_tagged(s->evs.data(), T, s->tags_r.as<int32_t>(), s->rows.as<int64_t>(), R,
-                             nullptr, s->rows_s.as<float>(), stream);
-    if (rc) return rc;
+    if (read_only) {
+      rc = dr_ev_gather_tagged_readonly(s->evs.data(), T, s->keys_r.as<int64_t>(),
+                                        s->tags_r.as<int32_t>(), R, nullptr, s->rows_s.p, stream);
+      if (rc) return rc;
+    } else {
+      rc = dr_ev_resolve_tagged(s->evs.data(), T, s->keys_r.as<int64_t>(),
+                                s->tags_r.as<int32_t>(), R, nullptr, per_table.data(), nullptr,
+                                s->rows.as<int64_t>(), s->ws.p, s->ws.bytes, stream);
+      if (rc) return rc;
+      rc = dr_ev_gather_tagged(s->evs.data(), T, s->tags_r.as<int32_t>(), s->rows.as<int64_t>(),
+                               R, nullptr, s->rows_s.as<float>(), stream);
+      if (rc) return rc;
+    }
   }
   // 6. rows back to the requesters
   rc = a2a_v(s->comm, s->rows_s.p, recv.data(), s->rows_r.p, send.data(), (int64_t)vrow, st);

@@ -134,6 +134,7 @@ class DrDinMlpBuf(C.Structure):
 
 RCCL_UNIQUE_ID_BYTES = 128
 SHARDED_OUT_BF16 = 1
+SHARDED_READ_ONLY = 2
 
 # name -> (restype, argtypes); must match include/deeprec_amd.h
 SIGNATURES = {
@@ -219,6 +220,7 @@ SIGNATURES = {
     "dr_ev_gather": (_I32, [_P, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
     "dr_ev_find_grouped": (_I32, [_P, _I32, _P, _P, _P, _P, _P]),
     "dr_ev_gather_readonly": (_I32, [_P, _P, _I64, _P, _P, _P]),
+    "dr_ev_gather_tagged_readonly": (_I32, [_P, _I32, _P, _P, _I64, _P, _P, _P]),
     "dr_ev_lookup_onehot_readonly": (_I32, [_P, _I32, _P, _I64, _I64, _I64, _P, _I64, _I32, _I32,
                                             _P, _P]),
     "dr_embedding_lookup_sparse_readonly_workspace_size": (_SZ, [_I64, _I64]),
@@ -284,6 +286,7 @@ SIGNATURES = {
     "dr_xgmi_route_ex": (_I32, [_P, _P, _I32, _I64, _P, _P, _P]),
     "dr_xgmi_serve_workspace_size": (_SZ, [_I32, _I64]),
     "dr_xgmi_serve": (_I32, [_P, _P, _I32, _I64, _P, _SZ, _P]),
+    "dr_xgmi_serve_readonly": (_I32, [_P, _P, _I32, _I64, _P]),
     "dr_xgmi_grad_pull_workspace_size": (_SZ, [_I32, _I64]),
     "dr_xgmi_grad_pull": (_I32, [_P, _P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _SZ, _P]),
     "dr_xgmi_grad_pull_dev_workspace_size": (_SZ, [_I32, _I64]),

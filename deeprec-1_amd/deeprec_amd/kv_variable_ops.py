@@ -178,7 +178,9 @@ class read_only_lookups(object):
     present, admitted id gives its row, any other the EV's default row; no
     key is created, no sighting counted, no table grown; results carry no
     grad_fn and nothing is queued in pending_grads.  Dense tables and
-    tensors behave as outside it."""
+    tensors behave as outside it.  The sharded lookup engines (sharded.py)
+    follow it too: their owners serve without inserting, and an id its
+    owner does not serve reads that OWNER's default row."""
 
     def __enter__(self):
         _READ_ONLY.depth = getattr(_READ_ONLY, "depth", 0) + 1

@@ -365,11 +365,16 @@ def _sharded_lookup(anchor, engine, ids):
     under torch.no_grad() (an eval pass) a plain forward that keeps no
     routing state (need_grad off: the engines' cheaper direct path)."""
     if read_only_active():
-        # the engines' owner side is insert-on-miss: serving here would create
-        # and count keys behind a context that promises not to
-        raise DeepRecError(INVALID_ARGUMENT,
-                           "read_only_lookups(): the sharded lookup engines have no read-only "
-                           "forward yet; evaluate on a local (unsharded) model")
+        if not getattr(engine, "supports_read_only", False):
+            # an insert-on-miss owner side would create and count keys behind
+            # a context that promises not to
+            raise DeepRecError(INVALID_ARGUMENT,
+                               "read_only_lookups(): this sharded lookup engine has no "
+                               "read-only forward; evaluate on a local (unsharded) model")
+        # no autograd node: the result carries no grad_fn, and a pending
+        # backward of an earlier forward must refuse (the buffers are reused)
+        engine._dr_fwd_gen = getattr(engine, "_dr_fwd_gen", 0) + 1
+        return engine.forward(ids, read_only=True)
     if torch.is_grad_enabled():
         return _ShardedLookupFn.apply(anchor, engine, ids)
     # this forward overwrites the engine's exchange buffers too: a pending

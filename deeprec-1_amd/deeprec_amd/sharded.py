@@ -64,8 +64,10 @@ class HipLocal(object):
         self.handles = (C.c_void_p * self.T)(*[e.handle.value for e in evs])
         self.filter = any(e.filter_freq != 0 for e in evs)
 
-    def unique_grouped(self, vals, koff):
-        return ops.unique_grouped(vals, koff, self.filter)
+    def unique_grouped(self, vals, koff, counts=None):
+        """counts: None = what the EVs need (filter EVs count sightings);
+        False = never (a read-only forward has no counts to merge)."""
+        return ops.unique_grouped(vals, koff, self.filter if counts is None else counts)
 
     def route(self, uniq, koff, num_unique, world):
         return ops.route_by_owner(uniq, koff, num_unique, world)
@@ -85,6 +87,19 @@ class HipLocal(object):
                                          None, ptr(rows), ptr(ws), wsb, st))
         check(lib().dr_ev_gather_tagged(self.handles, self.T, ptr(tags), ptr(rows), n, None,
                                         ptr(out), st))
+        ops._post(self.device)
+        return out
+
+    def find_pack(self, keys, tags, n):
+        """Owner side of a read-only forward: row pack of n received keys in
+        one launch (dr_ev_gather_tagged_readonly) -- a present, admitted key
+        gives its row, any other this owner's default row of its table; no
+        EV is changed, and there is no row array and no workspace."""
+        out = torch.empty((n, self.dim), dtype=self.value_dtype, device=self.device)
+        if n == 0:
+            return out
+        check(lib().dr_ev_gather_tagged_readonly(self.handles, self.T, ptr(keys), ptr(tags), n,
+                                                 None, ptr(out), stream_handle(self.device)))
         ops._post(self.device)
         return out
 
@@ -163,8 +178,27 @@ class HipLocal(object):
         return out
 
 
+def _want_read_only(read_only, need_grad=False):
+    """forward(read_only=None) of the engines: None follows the thread's
+    read_only_lookups() context."""
+    if read_only is None:
+        from .kv_variable_ops import read_only_active
+        read_only = read_only_active()
+    if read_only and need_grad:
+        raise ValueError("a read-only forward keeps no state for a backward (need_grad=True)")
+    return bool(read_only)
+
+
 class ShardedLookup(object):
-    """All-to-all row-sharded embedding_lookup_sparse over T features."""
+    """All-to-all row-sharded embedding_lookup_sparse over T features.
+
+    forward(read_only=True), or any forward inside read_only_lookups(), is
+    the evaluation / serving forward: the owners serve their received keys
+    with the backend's find_pack -- a present, admitted key gives its row,
+    any other the OWNER's EV default row (with a random initializer the
+    ranks' default rows differ) -- and no EV on any rank is changed."""
+
+    supports_read_only = True
 
     def __init__(self, evs, world, rank, batch, device, backend=None, group=None):
         self.evs = evs
@@ -183,12 +217,20 @@ class ShardedLookup(object):
         dist.all_to_all_single(out, inp, out_splits, in_splits, group=self.group)
         return out
 
-    def forward(self, ids, bag_offs=None, combiner="sum", need_grad=False, out_dtype=None):
+    def forward(self, ids, bag_offs=None, combiner="sum", need_grad=False, out_dtype=None,
+                read_only=None):
         """ids: [T, nnz] keys (hotness 1 when bag_offs is None: bag b = id b).
 
         Forward-only one-hot lookups of filter-free EVs route the raw ids
         (no Unique): the owner's insert-on-miss resolve dedups, exactly as
-        in the single-GPU direct mode (embedding_ops._prepare_group)."""
+        in the single-GPU direct mode (embedding_ops._prepare_group).
+
+        read_only (None: inside read_only_lookups()): nothing is inserted or
+        counted on any owner; a key that is absent or not admitted gets the
+        owner's default row.  One-hot ids then route directly for filter EVs
+        too (there are no counts to merge); multi-hot keeps the Unique (fewer
+        link bytes), without counts.  Not with need_grad; no backward state."""
+        ro = _want_read_only(read_only, need_grad)
         T, G, be = self.T, self.world, self.backend
         dev = ids.device
         nnz = ids.shape[1]
@@ -196,21 +238,29 @@ class ShardedLookup(object):
             raise ValueError("one-hot ids need nnz == batch (%d != %d)" % (nnz, self.batch))
         vals = ids.reshape(-1)
         koff = [t * nnz for t in range(T + 1)]
-        direct = bag_offs is None and not need_grad and not be.filter
+        direct = bag_offs is None and not need_grad and (ro or not be.filter)
         if G == 1 and direct and isinstance(be, HipLocal):
             # a single rank owns every key: no exchange with itself, the
-            # local fused lookup (same association order, same EV updates)
+            # local fused lookup (same association order, same EV updates;
+            # read-only: the local read-only lookup)
             from .embedding_ops import SparseTensor, embedding_lookup_sparse_multi
+            from .kv_variable_ops import read_only_lookups
             ind = torch.stack([torch.arange(nnz, device=dev),
                                torch.zeros(nnz, dtype=torch.int64, device=dev)], 1)
             sps = [SparseTensor(ind, ids[t], (self.batch, 1)) for t in range(T)]
             self.last_stats = {"sent_keys": 0, "recv_keys": 0, "direct": True, "local": True}
             self._saved = None
             with torch.no_grad():
+                if ro:
+                    with read_only_lookups():
+                        return embedding_lookup_sparse_multi(self.evs, sps, combiner=combiner,
+                                                             out_dtype=out_dtype)
                 return embedding_lookup_sparse_multi(self.evs, sps, combiner=combiner,
                                                      out_dtype=out_dtype)
         if direct:
             uniq, idx, U = vals, None, None
+        elif ro:
+            uniq, idx, _cnt, U = be.unique_grouped(vals, koff, counts=False)
         else:
             uniq, idx, _cnt, U = be.unique_grouped(vals, koff)
         keys_s, tags_s, perm, counts = be.route(uniq, koff, U, G)
@@ -230,7 +280,10 @@ class ShardedLookup(object):
             torch.arange(T, dtype=torch.int32, device=dev).repeat(G),
             recv_counts.view(-1), output_size=R)
         # 5. owner resolve + pack, 6. rows all-to-all back
-        rows_s = be.resolve_pack(keys_r, tags_r, R, rc.sum(0).tolist())
+        if ro:
+            rows_s = be.find_pack(keys_r, tags_r, R)
+        else:
+            rows_s = be.resolve_pack(keys_r, tags_r, R, rc.sum(0).tolist())
         rows_r = torch.empty((S, self.dim), dtype=rows_s.dtype, device=dev)
         self._a2a(rows_r, rows_s, send_splits, recv_splits)
         # 7. requester: (unique | nnz) position -> row in the received buffer
@@ -240,7 +293,7 @@ class ShardedLookup(object):
             out = be.pool(rows_r, rowsel, idx, koff, bag_offs, self.batch, combiner)
         else:
             out = be.pool(rows_r, rowsel, idx, koff, bag_offs, self.batch, combiner, out_dtype)
-        self.last_stats = {"sent_keys": S, "recv_keys": R, "direct": direct}
+        self.last_stats = {"sent_keys": S, "recv_keys": R, "direct": direct, "read_only": ro}
         self._saved = None
         if need_grad:
             self._saved = dict(idx=idx, koff=koff, U=U, perm=perm[:S], keys_r=keys_r, rc=rc,
@@ -407,7 +460,14 @@ class NativeShardedLookup(object):
     all-to-all, owner insert-on-miss resolve + row pack, row all-to-all back,
     ALI-order pooling; the owner's IndexedSlices in the backward -- with the
     sequence inside the C library, as a TF custom-op kernel would drive it
-    (INTEGRATION.md)."""
+    (INTEGRATION.md).
+
+    forward(read_only=True), or any forward inside read_only_lookups(), sets
+    DR_SHARDED_READ_ONLY: the owners serve without inserting or counting, a
+    key that is absent or not admitted gets the OWNER's EV default row (with
+    a random initializer the ranks' default rows differ)."""
+
+    supports_read_only = True
 
     def __init__(self, comm, evs, device, kind="rccl", batch=0, max_ids=0):
         """kind: "rccl" (dr_sharded_create: exact-size all-to-alls, host reads
@@ -446,11 +506,14 @@ class NativeShardedLookup(object):
         return self._out_view[2]
 
     def forward(self, ids, bag_offs=None, combiner="sum", need_grad=False, out_dtype=None,
-                copy=True):
+                copy=True, read_only=None):
         """ids: [T, B] int64 (one-hot, bag_offs None) or T 1-D int64 tensors
         (table t's ids); bag_offs None or T int32 [bags + 1] offsets covering
         each table's ids.  Returns [bags, T*D] (fp32; bf16 on request for bf16
-        EVs)."""
+        EVs).  read_only (None: inside read_only_lookups()): no EV is changed,
+        the owner's default row stands in for a key it does not serve; not
+        with need_grad, and a backward() after it refuses."""
+        ro = _want_read_only(read_only, need_grad)
         T = self.T
         flat = None
         if torch.is_tensor(ids):
@@ -478,7 +541,9 @@ class NativeShardedLookup(object):
                               device=self.device)
         ka = (C.c_int64 * (T + 1))(*koff)
         check(lib().dr_sharded_forward(self.h, ptr(flat), ka, offs, bags, COMBINERS[combiner],
-                                       1 if need_grad else 0, _lib.SHARDED_OUT_BF16 if bf else 0,
+                                       1 if need_grad else 0,
+                                       (_lib.SHARDED_OUT_BF16 if bf else 0) |
+                                       (_lib.SHARDED_READ_ONLY if ro else 0),
                                        ptr(out), stream_handle(self.device)))
         if out is None:
             out = self.output()
@@ -832,7 +897,15 @@ class XgmiShardedLookup(object):
     served into the staging buffer, then the ALI-order segment pooling over
     the bags (SparseSegmentReduction, segment_reduction_ali_ops_util.h:193-
     318); backward: each unique key's SparseSegment*Grad sum, pulled by its
-    owner.  No host read in either direction."""
+    owner.  No host read in either direction.
+
+    forward(read_only=True), or any forward inside read_only_lookups(): the
+    owners run serve_readonly() (dr_xgmi_serve_readonly, one launch) in place
+    of serve() on every path above -- nothing is inserted, a key the owner
+    does not hold gets the OWNER's EV default row (with a random initializer
+    the ranks' default rows differ) -- and a backward() after it refuses."""
+
+    supports_read_only = True
 
     def __init__(self, evs, world, rank, batch, device, group=None, peer_buffers=None,
                  barrier=None, buffers=None, dedup=False):
@@ -883,6 +956,7 @@ class XgmiShardedLookup(object):
         self._koff = [t * batch for t in range(self.T + 1)]
         self._tcol = torch.arange(self.T, dtype=torch.int64, device=device)[:, None]
         self._saved = None
+        self._ro_last = False    # the last forward was read-only: no backward
 
     def _exchange_ipc(self):
         mine = []
@@ -929,6 +1003,19 @@ class XgmiShardedLookup(object):
                                   ptr(self.ws), self.wsb, stream_handle(self.device)))
         ops._post(self.device)
 
+    def serve_readonly(self):
+        """serve() without insert-on-miss: one launch, no workspace."""
+        check(lib().dr_xgmi_serve_readonly(C.byref(self.peers), self.handles, self.T, self.batch,
+                                           stream_handle(self.device)))
+        ops._post(self.device)
+
+    def _serve(self, ro):
+        self._ro_last = ro
+        if ro:
+            self.serve_readonly()
+        else:
+            self.serve()
+
     def backward(self, grad_out):
         """grad_out: [B, T*D] gradient of the last forward().
 
@@ -943,6 +1030,9 @@ class XgmiShardedLookup(object):
         per-table (keys, grads, count) -- count a DEVICE int64[1]; the first
         count rows of keys / grads are the slice."""
         from .kv_variable_ops import IndexedSlices
+        if self._ro_last:
+            raise RuntimeError("backward() needs a training forward() first (the last forward "
+                               "was read-only)")
         g = grad_out.contiguous()
         T, D, B, W = self.T, self.dim, self.batch, self.world
         if not g.is_floating_point() or (self._saved is None and tuple(g.shape) != (B, T * D)):
@@ -981,16 +1071,20 @@ class XgmiShardedLookup(object):
             self.evs[t].pending_grads.append(IndexedSlices(v, k, num_valid=n, unique=False))
         return out
 
-    def forward(self, ids, out_dtype=None, bag_offs=None, combiner="sum"):
+    def forward(self, ids, out_dtype=None, bag_offs=None, combiner="sum", read_only=None):
         """ids: [T, B] int64 keys (hotness 1) -> [B, T*D] pooled (sum).  bf16
         EVs travel as bf16 rows (half the link bytes); the result is widened
         to fp32 (the reference's cast) unless out_dtype=torch.bfloat16, which
         returns the peer-written bf16 buffer itself.
 
         Multi-hot: ids [T, nnz] (nnz <= batch), bag_offs = T int32 [bags+1]
-        offset arrays -> [bags, T*D] pooled with `combiner` (a new tensor)."""
+        offset arrays -> [bags, T*D] pooled with `combiner` (a new tensor).
+
+        read_only (None: inside read_only_lookups()): the owners serve
+        without inserting (serve_readonly); no backward state is kept."""
+        ro = _want_read_only(read_only)
         if bag_offs is not None:
-            return self._forward_bags(ids, bag_offs, combiner, out_dtype)
+            return self._forward_bags(ids, bag_offs, combiner, out_dtype, ro)
         if tuple(ids.shape) != (self.T, self.batch) or ids.dtype != torch.int64:
             raise ValueError("ids must be int64 [%d, %d]" % (self.T, self.batch))
         ids = ids.contiguous()
@@ -999,11 +1093,11 @@ class XgmiShardedLookup(object):
             uniq, idx, _, U = ops.unique_grouped(ids.view(-1), self._koff, False)
             self.route(uniq, n_dev=U)
             self._barrier()
-            self.serve()
+            self._serve(ro)
             self._barrier()
             # expand: bag (b, t) reads the staging row of its unique key
             rowsel = (idx.view(T, B).to(torch.int64) * T + self._tcol).view(-1)
-            self._saved = (idx, U, self._koff, None, B, "sum")
+            self._saved = None if ro else (idx, U, self._koff, None, B, "sum")
             return self._local.pool(self.bufs.out.view(B * T, self.dim), rowsel, None,
                                     self._koff, None, B, "sum", out_dtype)
         self._saved = None
@@ -1017,7 +1111,7 @@ class XgmiShardedLookup(object):
         self._barrier()
         if ph is not None:
             ev[2].record()
-        self.serve()
+        self._serve(ro)
         if ph is not None:
             ev[3].record()
         self._barrier()
@@ -1054,7 +1148,7 @@ class XgmiShardedLookup(object):
         out["steps"] = n
         return out
 
-    def _forward_bags(self, ids, bag_offs, combiner, out_dtype):
+    def _forward_bags(self, ids, bag_offs, combiner, out_dtype, ro=False):
         T, B = self.T, self.batch
         if ids.dim() != 2 or ids.shape[0] != T or ids.dtype != torch.int64 or ids.shape[1] > B:
             raise ValueError("multi-hot ids must be int64 [%d, nnz <= %d]" % (T, B))
@@ -1075,12 +1169,12 @@ class XgmiShardedLookup(object):
                 keys[:, :nnz] = uniq.view(T, nnz)
         self.route(keys, n_dev=U)
         self._barrier()
-        self.serve()
+        self._serve(ro)
         self._barrier()
         # expand: position i of table t reads the staging row u*T + t of its
         # unique key u, pooled over its bag in the ALI order
         rowsel = (idx.view(T, nnz).to(torch.int64) * T + self._tcol).view(-1)
-        self._saved = (idx, U, koff, list(bag_offs), bags, combiner)
+        self._saved = None if ro else (idx, U, koff, list(bag_offs), bags, combiner)
         return self._local.pool(self.bufs.out.view(B * T, self.dim), rowsel, None, koff,
                                 bag_offs, bags, combiner, out_dtype)
 

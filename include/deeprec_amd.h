@@ -521,6 +521,16 @@ int dr_ev_find_grouped(dr_ev* const* evs, int num_tables, const int64_t* keys,
 /* EV's value_bits.                                                          */
 int dr_ev_gather_readonly(dr_ev* ev, const int64_t* keys, int64_t n, const void* defaults,
                           void* out, void* stream);
+/* Tagged gather, the owner-side pack of the sharded engines' read-only      */
+/* forward (the read-only counterpart of dr_ev_resolve_tagged +              */
+/* dr_ev_gather_tagged, in one launch and without a workspace): out[i] = the */
+/* row of keys[i] in table tags[i], or that table's default row; n_dev       */
+/* (DEVICE, nullable) limits it to the first *n_dev entries, the rest of out */
+/* is not written.  The tables share row words and value type (bf16 rows     */
+/* move bitwise); out is [n, dim] of that type.                              */
+int dr_ev_gather_tagged_readonly(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                                 const int32_t* tags, int64_t n, const int64_t* n_dev, void* out,
+                                 void* stream);
 /* Fused one-hot lookup (arguments and DR_LOOKUP_* flags of                  */
 /* dr_ev_lookup_onehot_ex; no workspace).  One kernel: a key that is not     */
 /* served reads its table's default row, rows_out (nullable) gets -1 for it. */
@@ -874,6 +884,15 @@ int dr_xgmi_route_ex(const dr_xgmi_peers* peers, const int64_t* keys, int num_ta
 size_t dr_xgmi_serve_workspace_size(int world, int64_t cap);
 int dr_xgmi_serve(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
                   int64_t batch, void* ws, size_t ws_bytes, void* stream);
+/* The owner side read-only (EmbeddingVar::Lookup: evaluation and serving), */
+/* between the same two barriers: an inbox key that is present, published   */
+/* and admitted (the rules of dr_ev_gather_readonly) gets its stored row,   */
+/* any other the OWNER's default row of that table; nothing is created,     */
+/* counted or grown, so no reserve and no workspace.  One launch.  The same */
+/* peer, dim and value-type checks as dr_xgmi_serve; filter EVs are         */
+/* accepted (admission is one more load).                                   */
+int dr_xgmi_serve_readonly(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
+                           int64_t batch, void* stream);
 /* Backward of the peer-write lookup, owner side: this rank's inbox entries  */
 /* (cnt_host[s] of source s, read by the caller from its inbox counts),      */
 /* sorted by (table, source, slot), each pulling the requester's gradient    */
@@ -963,7 +982,16 @@ int dr_sharded_destroy(dr_sharded* s);
 /* dedups, SOK's all2all_input_dispatcher), otherwise the grouped Unique     */
 /* runs first (embedding_ops.py:592-596).  One host read of the split sizes */
 /* per direction (SOK syncs there too, all2all_input_dispatcher.cu:256-268). */
+/* DR_SHARDED_READ_ONLY (every kind): a forward for evaluation and serving.  */
+/* The requester side is the same (route, exchanges, pooling); the owners    */
+/* serve their received keys with dr_ev_gather_tagged_readonly (XGMI:        */
+/* dr_xgmi_serve_readonly) -- a present, admitted key gives its row, any     */
+/* other the OWNER's default row of the table (ranks whose default rows      */
+/* differ serve different defaults); no EV on any rank is changed.  Not with */
+/* need_grad (DR_INVALID_ARGUMENT); it keeps no state, so a backward after   */
+/* it refuses like one without a gradient forward.                           */
 #define DR_SHARDED_OUT_BF16 1
+#define DR_SHARDED_READ_ONLY 2
 int dr_sharded_forward(dr_sharded* s, const int64_t* ids, const int64_t* koff_host,
                        const int32_t* const* bag_off, int64_t bags, int combiner, int need_grad,
                        int flags, void* out, void* stream);
