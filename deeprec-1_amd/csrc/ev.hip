@@ -17,6 +17,8 @@
 //                   bitset (bits 48..63); key -1 lives in slots[cap].
 //   pool[c]         [row_cap, dim] fp32 rows of column c (0 = primary).
 //   freq/version    [row_cap] int64, only when filter / steps_to_live on.
+//   dirty           [ceil(row_cap / 32)] uint32, one bit per row, only while update
+//                   tracking is on (incremental checkpoints, below).
 // A key owns one row id for all columns; a column's row is initialised from
 // that column's default the first time it is touched, exactly like the
 // reference's lazily allocated per-emb_index rows.
@@ -61,6 +63,9 @@ struct EvShared {
   int64_t row_cap = 0;
   int64_t* freq = nullptr;
   int64_t* version = nullptr;
+  // update tracking (dr_ev_track_updates): one bit per row, ceil(row_cap / 32)
+  // words; nullptr while tracking is off
+  uint32_t* dirty = nullptr;
   float* pools[kMaxCols] = {nullptr};
   float* defaults[kMaxCols] = {nullptr};
   void* bloom = nullptr;
@@ -104,6 +109,9 @@ struct EvShared {
   // host side of every call on this EV (EvGuard below)
   std::recursive_mutex api_mu;
 };
+
+// uint32 words of the update-tracking bitmap of `row_cap` rows
+inline int64_t dirty_words(int64_t row_cap) { return (row_cap + 31) / 32; }
 
 // float words per row of column `col`
 inline int64_t col_words(const EvShared* s, int col) {
@@ -1324,6 +1332,7 @@ static void free_shared(EvShared* s) {
   (void)hipFree(s->top);
   (void)hipFree(s->freq);
   (void)hipFree(s->version);
+  (void)hipFree(s->dirty);
   for (int c = 0; c < kMaxCols; ++c) {
     (void)hipFree(s->pools[c]);
     (void)hipFree(s->defaults[c]);
@@ -1421,6 +1430,16 @@ static int grow(EvShared* s, int64_t need, hipStream_t st) {
       DR_HIP(hipStreamSynchronize(st));
       DR_HIP(hipFree(*a));
       *a = np;
+    }
+    if (s->dirty) {  // old bits kept, the new rows' bits zero
+      uint32_t* np = nullptr;
+      DR_HIP(hipMalloc(&np, (size_t)dirty_words(nrc) * sizeof(uint32_t)));
+      int frc = fill_bytes(np, 0, (size_t)dirty_words(nrc) * sizeof(uint32_t), st);
+      if (frc) return frc;
+      DR_HIP(grow_copy(np, s->dirty, (size_t)dirty_words(s->row_cap) * sizeof(uint32_t), st));
+      DR_HIP(hipStreamSynchronize(st));
+      DR_HIP(hipFree(s->dirty));
+      s->dirty = np;
     }
     s->row_cap = nrc;
   }
@@ -3629,6 +3648,394 @@ int dr_ev_apply_adam(dr_ev* var, dr_ev* m, dr_ev* v, float beta1_power, float be
   dr::OptScalars sc = {lr, beta1, beta2, epsilon, alpha, 0, 0, 0, 0};
   return dr::apply_common(dr::OPT_ADAM, var, m, v, sc, grad, keys, n, n_dev, global_step,
                           dr::S(stream));
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Update tracking, delta export and upsert: incremental checkpoints.  These
+// play the roles of the reference's RecordSparseIndices / IncrSave /
+// KvResourceIncrImport; the semantics are build-defined.
+// A key space that tracks updates holds one bit per row (EvShared::dirty).
+// Rows are never recycled and both growth and dr_ev_shrink keep a key's row,
+// so a bit stays with its key for the key's lifetime; the bit of an evicted
+// key stays set and selects nothing.
+//   mark   : lane per key, the read-only probe of the primary column, atomicOr
+//   export : scan the cap + 1 slots (16-B loads, wave ballots, one append per
+//            block tile), radix sort on the sign-flipped key, gather
+//   upsert : ev_import_kernel, then every accepted row is written
+// ===========================================================================
+namespace dr {
+
+struct MarkGroup {
+  LkDesc d[DR_MAX_GROUP];     // the PRIMARY column's probe view
+  uint32_t* bits[DR_MAX_GROUP];  // nullptr: the table's key space is not tracking
+  int64_t row_cap[DR_MAX_GROUP];
+  int64_t koff[DR_MAX_GROUP + 1];
+  const int64_t* n_dev[DR_MAX_GROUP];
+};
+static_assert(sizeof(MarkGroup) + 64 <= 4096, "mark kernel arguments exceed 4 KiB");
+
+__global__ __launch_bounds__(256) void ev_mark_updated_kernel(MarkGroup g, int T,
+                                                              const int64_t* __restrict__ keys) {
+  __shared__ LkDesc sd[DR_MAX_GROUP];
+  __shared__ uint32_t* sb[DR_MAX_GROUP];
+  __shared__ int64_t sr[DR_MAX_GROUP];
+  if (threadIdx.x < T) {
+    sd[threadIdx.x] = g.d[threadIdx.x];
+    sb[threadIdx.x] = g.bits[threadIdx.x];
+    sr[threadIdx.x] = g.row_cap[threadIdx.x];
+  }
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.koff[T]) return;
+  const int t = table_of(g.koff, T, i, (int64_t)blockIdx.x * blockDim.x);
+  const int64_t li = i - g.koff[t];
+  if (g.n_dev[t] && li >= *g.n_dev[t]) return;
+  uint32_t* bits = sb[t];
+  if (!bits) return;
+  const int64_t row = ev_probe_row(sd[t], (uint64_t)keys[i]);
+  if (row < 0 || row >= sr[t]) return;
+  uint32_t* w = bits + (row >> 5);
+  const uint32_t m = 1u << (row & 31);
+  if (!(gld(w) & m)) atomicOr(w, m);  // (a repeated key finds its bit set)
+}
+
+__global__ __launch_bounds__(256) void ev_dirty_count_kernel(const uint32_t* __restrict__ bits,
+                                                             int64_t nw,
+                                                             unsigned long long* __restrict__ total) {
+  unsigned long long c = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw;
+       i += (int64_t)gridDim.x * blockDim.x)
+    c += (unsigned)__popc(gld(bits + i));
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  if (lane_id() == 0 && c) atomicAdd(total, c);
+}
+
+// The dr_ev_export selection (occupied, published, live, primary bit and this
+// column's bit -- `need`) narrowed to rows whose bit is set.  A block takes a
+// tile of 256 * kUpdItems slots, one coalesced 16-B load per lane and item,
+// counts its hits (wave ballots, wave totals in LDS) and reserves their places
+// with ONE atomic add: tens of thousands of wave-level adds on the one counter
+// would serialise.  Appends (key ^ sign, row, position); the sort that follows
+// makes the result independent of the append order.
+static constexpr int kUpdItems = 8;
+
+__global__ __launch_bounds__(256) void ev_scan_updated_kernel(
+    const Slot* __restrict__ slots, int64_t cap, uint64_t need, const uint32_t* __restrict__ bits,
+    int64_t row_cap, uint64_t* __restrict__ kout, int64_t* __restrict__ rout,
+    int32_t* __restrict__ iout, int64_t bound, unsigned long long* __restrict__ count) {
+  __shared__ unsigned wtot[4];
+  __shared__ unsigned long long sbase;
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t tile = (int64_t)blockIdx.x * (256 * kUpdItems);
+  uint64_t key[kUpdItems];
+  int64_t row[kUpdItems];
+  uint64_t mask[kUpdItems];  // wave-uniform
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < kUpdItems; ++j) {
+    const int64_t i = tile + j * 256 + threadIdx.x;
+    bool hit = false;
+    key[j] = 0;
+    row[j] = 0;
+    if (i <= cap) {
+      const slot_v sv = gld(reinterpret_cast<const slot_v*>(slots + i));
+      const bool occupied = i < cap ? sv.x != kEmptyKey : sv.x == 0ull;
+      if (occupied && sv.y != kUnset && (sv.y & kRowMask) != kRowDead && (sv.y & need) == need) {
+        row[j] = (int64_t)(sv.y & kRowMask);
+        if (row[j] < row_cap && ((gld(bits + (row[j] >> 5)) >> (row[j] & 31)) & 1u)) {
+          hit = true;
+          key[j] = i < cap ? sv.x : kEmptyKey;  // the special slot holds key -1
+        }
+      }
+    }
+    mask[j] = __ballot(hit);
+    mine += (unsigned)__popcll(mask[j]);
+  }
+  if (lane == 0) wtot[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    sbase = t ? atomicAdd(count, (unsigned long long)t) : 0ull;
+  }
+  __syncthreads();
+  int64_t pos = (int64_t)sbase;
+  for (int w = 0; w < wave; ++w) pos += wtot[w];
+#pragma unroll
+  for (int j = 0; j < kUpdItems; ++j) {
+    if ((mask[j] >> lane) & 1ull) {
+      const int64_t p = pos + __popcll(mask[j] & lanemask_lt());
+      if (p < bound) {
+        kout[p] = key[j] ^ (1ull << 63);
+        rout[p] = row[j];
+        iout[p] = (int32_t)p;
+      }
+    }
+    pos += __popcll(mask[j]);
+  }
+}
+
+// Sorted (key ^ sign, position) -> keys, rows (for the row gather), versions
+// and freqs (0 where the EV keeps none).
+__global__ __launch_bounds__(256) void ev_export_meta_kernel(
+    const uint64_t* __restrict__ ks, const int32_t* __restrict__ is,
+    const int64_t* __restrict__ rbuf, int64_t m, const int64_t* __restrict__ version,
+    const int64_t* __restrict__ freq, int64_t* __restrict__ keys_out,
+    int64_t* __restrict__ rows_out, int64_t* __restrict__ versions_out,
+    int64_t* __restrict__ freqs_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const int64_t row = rbuf[is[i]];
+  rows_out[i] = row;
+  if (keys_out) keys_out[i] = (int64_t)(ks[i] ^ (1ull << 63));
+  if (versions_out) versions_out[i] = version ? gld(version + row) : 0;
+  if (freqs_out) freqs_out[i] = freq ? gld(freq + row) : 0;
+}
+
+// pool[rows[i]] = values[i] for every key the import accepted (rows[i] >= 0),
+// G lanes per row, float words moved bitwise.
+template <int G>
+__global__ __launch_bounds__(256) void ev_upsert_rows_kernel(float* __restrict__ pool,
+                                                             int64_t words,
+                                                             const float* __restrict__ values,
+                                                             const int64_t* __restrict__ rows,
+                                                             int64_t n, int64_t row_cap, int vec) {
+  const int64_t i = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  if (i >= n) return;
+  const int64_t r = rows[i];
+  if (r < 0 || r >= row_cap) return;
+  ro_copy_row<G>(values + i * words, pool + r * words, words, vec, threadIdx.x % G);
+}
+
+// Device temporaries of one call from the stream's memory pool (as
+// dr_ev_insert takes them): no driver allocation and no device-wide
+// synchronisation per call.
+struct DevBuf {
+  void* p = nullptr;
+  hipStream_t st = nullptr;
+  hipError_t alloc(size_t bytes, hipStream_t s) {
+    st = s;
+    return hipMallocAsync(&p, bytes, s);
+  }
+  ~DevBuf() {
+    if (p) (void)hipFreeAsync(p, st);
+  }
+};
+
+static int dirty_count(EvShared* s, hipStream_t st, int64_t* out) {
+  DevBuf b;
+  DR_HIP(b.alloc(sizeof(unsigned long long), st));
+  int rc = fill_bytes(b.p, 0, sizeof(unsigned long long), st);
+  if (rc) return rc;
+  const int64_t nw = dirty_words(s->row_cap);
+  const int64_t blocks = std::min<int64_t>(std::max<int64_t>(ceil_div(nw, 256), 1), 1024);
+  hipLaunchKernelGGL(ev_dirty_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, s->dirty, nw,
+                     static_cast<unsigned long long*>(b.p));
+  DR_LAUNCH_CHECK();
+  unsigned long long c = 0;
+  DR_HIP(hipMemcpyAsync(&c, b.p, sizeof(c), hipMemcpyDeviceToHost, st));
+  DR_HIP(hipStreamSynchronize(st));
+  *out = (int64_t)c;
+  return DR_OK;
+}
+
+}  // namespace dr
+
+extern "C" {
+
+int dr_ev_track_updates(dr_ev* ev, int on, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev, DR_INVALID_ARGUMENT, "null ev");
+  EvShared* s = ev->sh;
+  hipStream_t st = S(stream);
+  if (on) {
+    DR_REQUIRE(s->k_hash == 0, DR_INVALID_ARGUMENT,
+               "update tracking is not available for Bloom-filter EVs (their export frequency "
+               "is a host-side counter walk)");
+    if (s->dirty) return DR_OK;
+    uint32_t* d = nullptr;
+    const size_t bytes = (size_t)std::max<int64_t>(dirty_words(s->row_cap), 1) * sizeof(uint32_t);
+    DR_HIP(hipMalloc(&d, bytes));
+    int rc = fill_bytes(d, 0, bytes, st);
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = DR_INTERNAL;
+    if (rc) {
+      (void)hipFree(d);
+      set_error("dr_ev_track_updates: clearing the bitmap failed");
+      return rc;
+    }
+    s->dirty = d;
+    return DR_OK;
+  }
+  if (!s->dirty) return DR_OK;
+  // marks other streams enqueued on the bitmap must be done before it goes
+  DR_HIP(hipDeviceSynchronize());
+  DR_HIP(hipFree(s->dirty));
+  s->dirty = nullptr;
+  return DR_OK;
+}
+
+int dr_ev_tracking_updates(dr_ev* ev) { return ev ? (ev->sh->dirty ? 1 : 0) : -1; }
+
+int dr_ev_mark_updated(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                       const int64_t* koff_host, const int64_t* const* n_dev_per_table,
+                       void* stream) {
+  using namespace dr;
+  const int T = num_tables;
+  DR_REQUIRE(evs && koff_host && T >= 1 && T <= DR_MAX_GROUP, DR_INVALID_ARGUMENT, "bad argument");
+  for (int t = 0; t < T; ++t) {
+    DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
+    DR_REQUIRE(koff_host[t] >= 0 && koff_host[t + 1] >= koff_host[t], DR_INVALID_ARGUMENT,
+               "koff must be non-decreasing from >= 0");
+  }
+  const int64_t total = koff_host[T];
+  DR_REQUIRE(total == 0 || keys, DR_INVALID_ARGUMENT, "null keys");
+  EvGuard guard_(evs, T);
+  if (total == 0) return DR_OK;
+  MarkGroup g;
+  memset(&g, 0, sizeof(g));
+  bool any = false;
+  for (int t = 0; t < T; ++t) {
+    const EvShared* s = evs[t]->sh;
+    g.d[t].slots = s->slots;
+    g.d[t].cap = s->cap;
+    g.d[t].pool = s->pools[0];
+    g.d[t].colbit = 1ull << 48;
+    g.bits[t] = s->dirty;
+    g.row_cap[t] = s->row_cap;
+    g.koff[t] = koff_host[t];
+    g.n_dev[t] = n_dev_per_table ? n_dev_per_table[t] : nullptr;
+    any = any || s->dirty;
+  }
+  g.koff[T] = total;
+  if (!any) return DR_OK;
+  hipLaunchKernelGGL(ev_mark_updated_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0,
+                     S(stream), g, T, keys);
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+int dr_ev_updated_count(dr_ev* ev, int64_t* bound_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && bound_host, DR_INVALID_ARGUMENT, "null argument");
+  DR_REQUIRE(ev->sh->dirty, DR_INVALID_ARGUMENT, "the EV's key space is not tracking updates");
+  return dirty_count(ev->sh, S(stream), bound_host);
+}
+
+int dr_ev_clear_updated(dr_ev* ev, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev, DR_INVALID_ARGUMENT, "null ev");
+  DR_REQUIRE(ev->sh->dirty, DR_INVALID_ARGUMENT, "the EV's key space is not tracking updates");
+  return fill_bytes(ev->sh->dirty, 0, (size_t)dirty_words(ev->sh->row_cap) * sizeof(uint32_t),
+                    S(stream));
+}
+
+int dr_ev_export_updated(dr_ev* ev, int64_t* keys_out, void* values_out, int64_t* versions_out,
+                         int64_t* freqs_out, int64_t capacity, int64_t* m_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && m_host, DR_INVALID_ARGUMENT, "null argument");
+  EvShared* s = ev->sh;
+  DR_REQUIRE(s->dirty, DR_INVALID_ARGUMENT, "the EV's key space is not tracking updates");
+  hipStream_t st = S(stream);
+  *m_host = 0;
+  // the popcount bounds the append buffers (a row belongs to one key)
+  int64_t bound = 0;
+  int rc = dirty_count(s, st, &bound);
+  if (rc) return rc;
+  if (bound == 0) return DR_OK;
+  DR_REQUIRE(bound < ((int64_t)1 << 31), DR_INVALID_ARGUMENT,
+             "dr_ev_export_updated: %lld updated rows, the sort takes < 2^31",
+             (long long)bound);
+  const size_t sort_ws = dr_sort_pairs_workspace_size(bound);
+  Carver sz(nullptr);
+  sz.take<unsigned long long>(1);
+  sz.take<uint64_t>(bound);
+  sz.take<int64_t>(bound);
+  sz.take<int32_t>(bound);
+  sz.take<uint64_t>(bound);
+  sz.take<int32_t>(bound);
+  sz.take<int64_t>(bound);
+  sz.take<char>(sort_ws);
+  DevBuf buf;
+  DR_HIP(buf.alloc(sz.used + 256, st));
+  Carver c(buf.p);
+  unsigned long long* cnt = c.take<unsigned long long>(1);
+  uint64_t* kbuf = c.take<uint64_t>(bound);
+  int64_t* rbuf = c.take<int64_t>(bound);
+  int32_t* ibuf = c.take<int32_t>(bound);
+  uint64_t* ksorted = c.take<uint64_t>(bound);
+  int32_t* isorted = c.take<int32_t>(bound);
+  int64_t* rows = c.take<int64_t>(bound);
+  char* ws = c.take<char>(sort_ws);
+  rc = fill_bytes(cnt, 0, sizeof(unsigned long long), st);
+  if (rc) return rc;
+  const uint64_t need = (1ull << 48) | (1ull << (48 + ev->col));
+  hipLaunchKernelGGL(ev_scan_updated_kernel,
+                     dim3((unsigned)ceil_div(s->cap + 1, 256 * kUpdItems)), dim3(256), 0, st,
+                     s->slots, s->cap, need, s->dirty, s->row_cap, kbuf, rbuf, ibuf, bound, cnt);
+  DR_LAUNCH_CHECK();
+  unsigned long long found = 0;
+  DR_HIP(hipMemcpyAsync(&found, cnt, sizeof(found), hipMemcpyDeviceToHost, st));
+  DR_HIP(hipStreamSynchronize(st));
+  const int64_t m = (int64_t)found;
+  DR_REQUIRE(m <= bound, DR_INTERNAL,
+             "dr_ev_export_updated: %lld entries for %lld marked rows (marks ran during the "
+             "export)", (long long)m, (long long)bound);
+  *m_host = m;
+  if (!keys_out && !values_out && !versions_out && !freqs_out) return DR_OK;
+  DR_REQUIRE(capacity >= m, DR_INVALID_ARGUMENT, "export capacity %lld < %lld",
+             (long long)capacity, (long long)m);
+  if (m == 0) return DR_OK;
+  rc = dr_sort_pairs(kbuf, ibuf, ksorted, isorted, m, 0, 64, ws, sort_ws, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ev_export_meta_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st,
+                     ksorted, isorted, rbuf, m, s->version, s->freq, keys_out, rows, versions_out,
+                     freqs_out);
+  DR_LAUNCH_CHECK();
+  if (values_out) {
+    rc = dr_gather(s->pools[ev->col], s->row_cap, col_words(s, ev->col), rows, m,
+                   static_cast<float*>(values_out), stream);
+    if (rc) return rc;
+  }
+  DR_HIP(hipStreamSynchronize(st));  // the temporaries go with this call
+  return DR_OK;
+}
+
+int dr_ev_upsert(dr_ev* ev, const int64_t* keys, int64_t n, const void* values,
+                 const int64_t* versions, const int64_t* freqs, int64_t partition_id,
+                 int64_t partition_num, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && n >= 0, DR_INVALID_ARGUMENT, "bad argument");
+  if (n == 0) return DR_OK;
+  DR_REQUIRE(keys && values, DR_INVALID_ARGUMENT, "null keys / values");
+  hipStream_t st = S(stream);
+  EvShared* s = ev->sh;
+  int rc = reserve(s, n, st);
+  if (rc) return rc;
+  int64_t* rows = nullptr;
+  uint8_t* init = nullptr;
+  DR_HIP(hipMallocAsync((void**)&rows, n * sizeof(int64_t), st));
+  DR_HIP(hipMallocAsync((void**)&init, n, st));
+  EvDesc e = make_desc(ev);
+  hipLaunchKernelGGL(ev_import_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, e, keys,
+                     n, versions, freqs, partition_id, partition_num, s->steps_to_live, rows, init,
+                     status_word());
+  // every accepted row is written, first touch or not: no default-row pass
+  const int64_t words = col_words(s, ev->col);
+  float* pool = s->pools[ev->col];
+  const int vec = words % 4 == 0 && ((uintptr_t)values | (uintptr_t)pool) % 16 == 0;
+  hipLaunchKernelGGL((ev_upsert_rows_kernel<16>), dim3((unsigned)ceil_div(n, 16)), dim3(256), 0, st,
+                     pool, words, static_cast<const float*>(values), rows, n, s->row_cap, vec);
+  DR_LAUNCH_CHECK();
+  DR_HIP(hipFreeAsync(rows, st));
+  DR_HIP(hipFreeAsync(init, st));
+  post_call(s, st);
+  return DR_OK;
 }
 
 }  // extern "C"

@@ -230,6 +230,13 @@ SIGNATURES = {
     "dr_ev_insert": (_I32, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _P]),
     "dr_ev_insert_synthetic": (_I32, [_P, _I64, _I64, _I64, _U64, _P]),
     "dr_ev_export": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P]),
+    "dr_ev_track_updates": (_I32, [_P, _I32, _P]),
+    "dr_ev_tracking_updates": (_I32, [_P]),
+    "dr_ev_mark_updated": (_I32, [_P, _I32, _P, _P, _P, _P]),
+    "dr_ev_updated_count": (_I32, [_P, _P, _P]),
+    "dr_ev_export_updated": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P]),
+    "dr_ev_clear_updated": (_I32, [_P, _P]),
+    "dr_ev_upsert": (_I32, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _P]),
     "dr_ev_key_meta": (_I32, [_P, _P, _I64, _P, _P, _P, _P]),
     "dr_ev_apply_sgd": (_I32, [_P, _F32, _P, _P, _I64, _P, _I64, _P]),
     "dr_ev_apply_adagrad": (_I32, [_P, _P, _F32, _P, _P, _I64, _P, _I64, _P]),

@@ -441,14 +441,17 @@ def dump_embedding_values(ev, tensor_key, writer):
     write_ev_tensors(writer, tensor_key, offs, keys, vals.reshape(-1, ev.dim), vers, frqs)
 
 
-def write_ev_tensors(writer, tensor_key, offs, keys, vals, vers, frqs):
+def write_ev_tensors(writer, tensor_key, offs, keys, vals, vers, frqs, suffix=""):
     """The five tensors of one EV, in DumpEmbeddingValues' write order
-    (partition_offset first, then keys, values, versions, freqs)."""
-    writer.add(tensor_key + "-partition_offset", offs)
-    writer.add(tensor_key + "-keys", keys)
-    writer.add(tensor_key + "-values", vals)
-    writer.add(tensor_key + "-versions", vers)
-    writer.add(tensor_key + "-freqs", frqs)
+    (partition_offset first, then keys, values, versions, freqs).  `suffix`
+    goes between the dash and the tensor's name: "" for a full save,
+    INCR_SUFFIX for a delta (NAME-sparse_incr_keys, ...)."""
+    pre = tensor_key + "-" + suffix
+    writer.add(pre + "partition_offset", offs)
+    writer.add(pre + "keys", keys)
+    writer.add(pre + "values", vals)
+    writer.add(pre + "versions", vers)
+    writer.add(pre + "freqs", frqs)
 
 
 def save(prefix, variables, global_step=None):
@@ -475,16 +478,18 @@ def _part_name(name, part, partition_id):
     return name[:i] + "part_" + str(part) + post
 
 
-def _import(ev, reader, tname, begin, end, filtered, partition_id, partition_num):
-    keys = reader.lookup_rows(tname + "-keys", begin, end)
+def _import(ev, reader, tname, begin, end, filtered, partition_id, partition_num, suffix="",
+            upsert=False):
+    tname = tname + "-" + suffix
+    keys = reader.lookup_rows(tname + "keys", begin, end)
     n = keys.shape[0]
     if n == 0:
         return
-    vals = reader.lookup_rows(tname + "-values", begin, end)
-    vshape = reader.entries[tname + "-versions"]["shape"]
-    vers = (reader.lookup_rows(tname + "-versions", begin, end) if vshape and vshape[0] > 0
+    vals = reader.lookup_rows(tname + "values", begin, end)
+    vshape = reader.entries[tname + "versions"]["shape"]
+    vers = (reader.lookup_rows(tname + "versions", begin, end) if vshape and vshape[0] > 0
             else np.full(n, -1, np.int64))
-    fkey = tname + "-freqs"
+    fkey = tname + "freqs"
     if reader.contains(fkey) and reader.entries[fkey]["shape"] and \
             reader.entries[fkey]["shape"][0] > 0:
         frqs = reader.lookup_rows(fkey, begin, end)
@@ -492,43 +497,47 @@ def _import(ev, reader, tname, begin, end, filtered, partition_id, partition_num
         frqs = np.full(n, ev.filter_freq, np.int64)          # MinFreq
     dev = ev.device
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    if filtered:
-        ev.import_partitioned(t(keys), t(vals), t(vers), t(frqs), partition_id, partition_num)
-    else:
-        ev.import_partitioned(t(keys), t(vals), t(vers), t(frqs), 0, 0)
+    if not filtered:
+        partition_id = partition_num = 0
+    put = ev._upsert if upsert else ev.import_partitioned
+    put(t(keys), t(vals), t(vers), t(frqs), partition_id, partition_num)
 
 
-def restore_embedding_variable(ev, reader, name, partition_id=0, partition_num=1):
-    """EVRestoreDynamically (kv_variable_ops.h:459-673)."""
+def restore_embedding_variable(ev, reader, name, partition_id=0, partition_num=1, suffix="",
+                               upsert=False):
+    """EVRestoreDynamically (kv_variable_ops.h:459-673).  `suffix` / `upsert`:
+    the same walk over a delta's NAME-sparse_incr_* tensors, ending in
+    EmbeddingVariable.upsert (restore_incremental)."""
+    sfx = "-" + suffix
     if isinstance(reader, str):
         reader = BundleReader(reader)
     if "part_" not in name:                                 # RestoreValue, no filter
-        n = reader.dtype_and_shape(name + "-keys")[1][0]
-        _import(ev, reader, name, 0, n, False, 0, 1)
+        n = reader.dtype_and_shape(name + sfx + "keys")[1][0]
+        _import(ev, reader, name, 0, n, False, 0, 1, suffix, upsert)
         return
-    new_form = reader.contains(_part_name(name, 0, partition_id) + "-partition_offset")
+    new_form = reader.contains(_part_name(name, 0, partition_id) + sfx + "partition_offset")
     part = 0
     while True:
         tname = _part_name(name, part, partition_id)
-        if not reader.contains(tname + "-keys"):
+        if not reader.contains(tname + sfx + "keys"):
             break
         if new_form:
-            for key in ("-values", "-versions"):
+            for key in (sfx + "values", sfx + "versions"):
                 # LookupHeader / LookupTensorShape fail on a missing tensor and
                 # EVRestoreDynamically treats that as fatal: raise, do not
                 # leave the EV half restored
                 if not reader.contains(tname + key):
                     raise _lib.DeepRecError(_lib.NOT_FOUND, "Key %s%s not found in checkpoint"
                                        % (tname, key))
-            offs = reader.lookup(tname + "-partition_offset")
+            offs = reader.lookup(tname + sfx + "partition_offset")
             for sub in range(partition_id % SAVED_PARTITION_NUM, SAVED_PARTITION_NUM,
                              partition_num):
                 if offs[sub + 1] > offs[sub]:
                     _import(ev, reader, tname, int(offs[sub]), int(offs[sub + 1]), True,
-                            partition_id, partition_num)
+                            partition_id, partition_num, suffix, upsert)
         else:                                               # DynamicRestoreValue
-            n = reader.dtype_and_shape(tname + "-keys")[1][0]
-            _import(ev, reader, tname, 0, n, True, partition_id, partition_num)
+            n = reader.dtype_and_shape(tname + sfx + "keys")[1][0]
+            _import(ev, reader, tname, 0, n, True, partition_id, partition_num, suffix, upsert)
         part += 1
 
 
@@ -537,3 +546,46 @@ def restore(prefix, variables, partition_id=0, partition_num=1):
     r = BundleReader(prefix)
     for name in variables:
         restore_embedding_variable(variables[name], r, name, partition_id, partition_num)
+
+
+# -- incremental checkpoints (build-defined) ----------------
+INCR_SUFFIX = "sparse_incr_"
+
+
+def save_incremental(prefix, variables, global_step=None):
+    """IncrSave's role: one bundle with, for every named EV (primaries and
+    slots), NAME-sparse_incr_{partition_offset, keys, values, versions,
+    freqs} holding the keys marked as updated since the key space was last
+    cleared (EmbeddingVariable.export_updated), in the full save's layout:
+    grouped by key % 1000, negative keys dropped, versions / freqs empty when
+    the EV keeps none.  Every key space must be tracking (track_updates()).
+    Each distinct key space is cleared once, after all of its columns are
+    written.  Nothing is shrunk -- eviction stays with the full save -- and
+    a delta does not carry evictions: an evicted key is simply absent from
+    it, so a replica drops it at its next full restore.  `global_step` is
+    accepted for symmetry with save() and unused.  Returns `prefix`."""
+    w = BundleWriter(prefix)
+    spaces = {}
+    for name in variables:
+        ev = variables[name]
+        keys, vals, vers, frqs = ev.export_updated()
+        offs, keys, vals, vers, frqs = partition_snapshot(keys, vals, vers, frqs)
+        write_ev_tensors(w, name, offs, keys, vals.reshape(-1, ev.dim), vers, frqs, INCR_SUFFIX)
+        p = ev._primary or ev
+        spaces[id(p)] = p
+    w.finish()
+    for p in spaces.values():
+        p.clear_updated()
+    return prefix
+
+
+def restore_incremental(prefix, variables, partition_id=0, partition_num=1):
+    """KvResourceIncrImport's role: apply a delta written by save_incremental
+    to {tensor_key: EmbeddingVariable}.  The walk of restore() (parts,
+    sub-partitions, the key % 1000 % partition_num filter) over the
+    NAME-sparse_incr_* tensors, ending in upsert: rows of keys already
+    present are overwritten, new keys are created."""
+    r = BundleReader(prefix)
+    for name in variables:
+        restore_embedding_variable(variables[name], r, name, partition_id, partition_num,
+                                   INCR_SUFFIX, True)

@@ -311,6 +311,7 @@ class EmbeddingVariable(object):
         self._primary = _primary
         self._slot_index = _slot_index
         self._lock = threading.Lock()
+        self._tracking = False    # update tracking of the key space (held by the primary)
         self.pending_grads = []
         opt = ev_option or EmbeddingVariableOption()
         f = opt.filter_option
@@ -544,6 +545,82 @@ class EmbeddingVariable(object):
             frqs = frqs[:0]
         return keys[:n], vals[:n], vers, frqs
 
+    # -- incremental checkpoints (build-defined) -----------
+    def _require_int64_keys(self, what):
+        if self.key_dtype != torch.int64:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "%s needs an int64-key EmbeddingVariable (%s has %s keys)"
+                % (what, self.name, self.key_dtype))
+
+    def track_updates(self, on=True):
+        """Start (or stop) recording which keys of the key space this EV
+        shares with its slots are updated: one bit per row, set by
+        mark_updated -- the optimizers' apply_gradients marks the gradient's
+        indices, RecordSparseIndices' role -- and read by export_updated."""
+        self._require_int64_keys("track_updates")
+        check(lib().dr_ev_track_updates(self._h, 1 if on else 0, stream_handle(self.device)))
+        (self._primary or self)._tracking = bool(on)
+
+    def tracking_updates(self):
+        """Whether this EV's key space records updates (the host-side mirror
+        of dr_ev_tracking_updates: no library call on the per-step path)."""
+        return (self._primary or self)._tracking
+
+    def mark_updated(self, keys, num_valid=None):
+        """Mark `keys` (the first num_valid of them: device int64[1]) as
+        updated.  Keys that are absent or whose primary row is untouched are
+        ignored, nothing is created; a no-op while tracking is off."""
+        mark_updated_grouped([self], [keys], [num_valid])
+
+    def updated_count(self):
+        """Number of marked rows: an upper bound on len(export_updated()[0])."""
+        n = C.c_int64(0)
+        check(lib().dr_ev_updated_count(self._h, C.byref(n), stream_handle(self.device)))
+        return n.value
+
+    def export_updated(self):
+        """export() narrowed to the marked keys: (keys, values, versions,
+        freqs), keys ascending.  Marks are left in place (clear_updated)."""
+        self._require_int64_keys("export_updated")
+        m = C.c_int64(0)
+        st = stream_handle(self.device)
+        # the marked-row count bounds the export: the buffers are sized by it
+        # and the slot table is scanned once, not once more for the count
+        check(lib().dr_ev_updated_count(self._h, C.byref(m), st))
+        M = m.value
+        keys = torch.empty(M, dtype=torch.int64, device=self.device)
+        vals = torch.empty((M, self.dim), dtype=self.value_dtype, device=self.device)
+        vers = torch.empty(M, dtype=torch.int64, device=self.device)
+        frqs = torch.empty(M, dtype=torch.int64, device=self.device)
+        if M:
+            check(lib().dr_ev_export_updated(self._h, ptr(keys), ptr(vals), ptr(vers), ptr(frqs),
+                                             M, C.byref(m), st))
+        n = m.value
+        if self.steps_to_live == 0:
+            vers = vers[:0]
+        if self.filter_freq == 0:
+            frqs = frqs[:0]
+        return keys[:n], vals[:n], vers[:n], frqs[:n]
+
+    def clear_updated(self):
+        check(lib().dr_ev_clear_updated(self._h, stream_handle(self.device)))
+
+    def upsert(self, keys, values, versions=None, freqs=None):
+        """insert() that OVERWRITES the rows of keys already present (insert
+        keeps them): how a delta is applied.  Keys must be distinct."""
+        return self._upsert(keys, values, versions, freqs, 0, 0)
+
+    def _upsert(self, keys, values, versions, freqs, pid, pnum):
+        self._require_int64_keys("upsert")
+        k = keys.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        v = values.reshape(k.numel(), self.dim).to(device=self.device,
+                                                   dtype=self.value_dtype).contiguous()
+        ver = None if versions is None else versions.to(device=self.device,
+                                                        dtype=torch.int64).contiguous()
+        fr = None if freqs is None else freqs.to(device=self.device, dtype=torch.int64).contiguous()
+        check(lib().dr_ev_upsert(self._h, ptr(k), k.numel(), ptr(v), ptr(ver), ptr(fr), pid, pnum,
+                                 stream_handle(self.device)))
+
     def key_meta(self, keys):
         """(freq, version, has_row) of keys, host numpy (tests/debug)."""
         import numpy as np
@@ -568,6 +645,31 @@ class EmbeddingVariable(object):
         check(lib().dr_ev_shrink(p._h, int(global_step), p.l2_weight_threshold, C.byref(n),
                                  stream_handle(self.device)))
         return n.value
+
+
+def mark_updated_grouped(evs, keys, num_valid=None):
+    """mark_updated over several EVs with one launch per device and
+    MAX_GROUP tables (dr_ev_mark_updated's grouping): keys[t], and the
+    optional device count num_valid[t], belong to evs[t].  EVs whose key
+    space is not tracking are left out."""
+    by_dev = {}
+    for t, ev in enumerate(evs):
+        if ev.tracking_updates() and keys[t].numel():
+            ev._require_int64_keys("mark_updated")
+            by_dev.setdefault(str(ev.device), []).append(
+                (ev, keys[t], None if num_valid is None else num_valid[t]))
+    for items in by_dev.values():
+        while items:
+            chunk, items = items[:_lib.MAX_GROUP], items[_lib.MAX_GROUP:]
+            dev, T = chunk[0][0].device, len(chunk)
+            ks = [k.reshape(-1).to(device=dev, dtype=torch.int64) for _, k, _ in chunk]
+            flat = ks[0].contiguous() if T == 1 else torch.cat(ks)
+            koff = (C.c_int64 * (T + 1))()
+            for t in range(T):
+                koff[t + 1] = koff[t] + ks[t].numel()
+            handles = (C.c_void_p * T)(*[ev._h.value for ev, _, _ in chunk])
+            nd = (C.c_void_p * T)(*[None if n is None else n.data_ptr() for _, _, n in chunk])
+            check(lib().dr_ev_mark_updated(handles, T, ptr(flat), koff, nd, stream_handle(dev)))
 
 
 _EV_REGISTRY = {}

@@ -15,7 +15,7 @@ from . import ops
 from ._lib import check, lib, ptr, stream_handle
 from .embedding_ops import DenseTable
 from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
-                              _flush_deferred_releases)
+                              _flush_deferred_releases, mark_updated_grouped)
 
 
 def _concat(slices):
@@ -119,6 +119,7 @@ class _Optimizer(object):
 
     def apply_gradients(self, var_list, global_step=None):
         gs = -1 if global_step is None else int(global_step)
+        self._record_updates(var_list)
         if self._opt == 0 and _KNOWN_ROWS:
             self._apply_fused_rows(var_list, gs)
         rounds = []   # rounds[r] = [(var, slices)] applied in one grouped launch
@@ -142,6 +143,21 @@ class _Optimizer(object):
             self._apply_ev_batch(items, gs)
         self._finish()
         _flush_deferred_releases()   # EVs collected meanwhile (no-op while capturing)
+
+    @staticmethod
+    def _record_updates(var_list):
+        """RecordSparseIndices' role (incremental_saver.py): every EV whose key
+        space tracks updates gets the indices of its pending slices marked
+        (honouring num_valid) before they are consumed.  Reading the indices
+        forms a PendingRowSlices' gradient, so a fused row group with a
+        tracked EV takes the ordinary path -- the same values.  Nothing runs
+        for an EV that is not tracking."""
+        marks = [(var, sl) for var in var_list
+                 if isinstance(var, EmbeddingVariable) and var.tracking_updates()
+                 for sl in var.pending_grads]
+        if marks:   # one launch per device and MAX_GROUP slices
+            mark_updated_grouped([var for var, _ in marks], [sl.indices for _, sl in marks],
+                                 [sl.num_valid for _, sl in marks])
 
     def _apply_fused_rows(self, var_list, gs):
         """SGD over every EV of a row-grouped lookup backward whose gradient

@@ -559,6 +559,61 @@ int dr_ev_insert_synthetic(dr_ev* ev, int64_t key_begin, int64_t key_stride, int
 int dr_ev_export(dr_ev* ev, int64_t* keys_out, float* values_out, int64_t* versions_out,
                  int64_t* freqs_out, int64_t capacity, int64_t* m_host, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Incremental checkpoints: update tracking, delta export, upsert.  They    */
+/* play the roles of the reference's RecordSparseIndices / IncrSave /       */
+/* KvResourceIncrImport (incremental_saver.py:77-494, io_ops.cc:282-316,    */
+/* kv_variable_ops.cc:719-783); the semantics below are build-defined.      */
+/* A primary EV and its slot EVs share one key space, and tracking is a     */
+/* property of that key space: one bit per row, ceil(row_capacity / 32)     */
+/* uint32 words, present only while tracking is on.  Rows are never         */
+/* recycled, so a bit stays with its key across growth and dr_ev_shrink.    */
+/* int64 keys only.                                                         */
+/* ------------------------------------------------------------------------ */
+/* on != 0: allocate and zero the bitmap; on == 0: free it.  Idempotent;    */
+/* may synchronise.  A Bloom-filter EV is refused (DR_INVALID_ARGUMENT):    */
+/* its export frequency is a host-side counter walk.                        */
+int dr_ev_track_updates(dr_ev* ev, int on, void* stream);
+/* 1 when the EV's key space tracks updates, 0 when not, -1 for a null EV.  */
+int dr_ev_tracking_updates(dr_ev* ev);
+/* Mark keys as updated (grouping of dr_ev_find_grouped: up to DR_MAX_GROUP */
+/* tables, koff_host prefix, optional per-table DEVICE counts).  One kernel: */
+/* the read-only probe of the PRIMARY column -- the key is in the map, its  */
+/* row published and live, the primary first-touch bit set; the Counter     */
+/* rule is not applied -- and on a hit an atomic OR of the row's bit.       */
+/* Nothing is inserted, counted, stamped or reserved.  Keys that miss are   */
+/* ignored, repeated keys are harmless, a table whose key space is not      */
+/* tracking is skipped.  Does not allocate or synchronise, so it may sit in */
+/* a captured step (valid until a table next grows, as every per-step       */
+/* call).                                                                   */
+int dr_ev_mark_updated(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                       const int64_t* koff_host, const int64_t* const* n_dev_per_table,
+                       void* stream);
+/* Number of marked rows: an UPPER BOUND on what dr_ev_export_updated       */
+/* returns (rows of evicted keys and rows whose column is untouched still   */
+/* count).  Syncs.                                                          */
+int dr_ev_updated_count(dr_ev* ev, int64_t* bound_host, void* stream);
+/* The entries of dr_ev_export whose row is marked, with dr_ev_export's     */
+/* contract: NULL outputs query the count into *m_host, capacity < m is     */
+/* DR_INVALID_ARGUMENT, keys ascending as signed int64, values in the EV's  */
+/* value type (rows move bitwise as float words: float, double, bf16),      */
+/* versions / freqs 0 where the EV keeps none.  Runs on the device (a scan  */
+/* of the 16 B x (capacity + 1) slot table, a radix sort, a gather); device */
+/* temporaries are allocated inside the call.  Syncs.  A key space that is  */
+/* not tracking is DR_INVALID_ARGUMENT.                                     */
+int dr_ev_export_updated(dr_ev* ev, int64_t* keys_out, void* values_out, int64_t* versions_out,
+                         int64_t* freqs_out, int64_t capacity, int64_t* m_host, void* stream);
+/* Zero the bitmap: one asynchronous launch, no sync.                       */
+int dr_ev_clear_updated(dr_ev* ev, void* stream);
+/* dr_ev_insert, except that the row of a key that already exists is        */
+/* OVERWRITTEN (dr_ev_insert keeps it).  Find-or-create, the freq clamp,    */
+/* the version store, the column bit and the partition filter are           */
+/* dr_ev_insert's.  values: [n, dim] in the EV's value type.  Keys must be  */
+/* distinct: with duplicates, which of their values lands is unspecified.   */
+int dr_ev_upsert(dr_ev* ev, const int64_t* keys, int64_t n, const void* values,
+                 const int64_t* versions, const int64_t* freqs, int64_t partition_id,
+                 int64_t partition_num, void* stream);
+
 /* Per-key freq / version of the primary, host-side, syncs (tests/debug).   */
 int dr_ev_key_meta(dr_ev* ev, const int64_t* keys_host, int64_t n, int64_t* freq_host,
                    int64_t* version_host, int32_t* has_row_host, void* stream);
