@@ -94,7 +94,7 @@ struct EvShared {
   bool copy_exact = false;
   hipEvent_t copy_ev = nullptr;
   int64_t* pinned_top = nullptr;
-  int64_t removed = 0;  // keys removed by dr_ev_shrink (rows are not recycled)
+  int64_t removed = 0;  // keys removed by dr_ev_shrink whose rows dr_ev_compact has not reclaimed
   // value dtype: 1 = float, 2 = double (a double row is stored as 2 * dim
   // float words and moved bitwise; `dim` counts float words)
   int value_words = 1;
@@ -1162,8 +1162,9 @@ __global__ __launch_bounds__(256) void ev_apply_ftrl_kernel(ApplyGroup ag, int64
 //   else, steps_to_live > 0   : version == -1 -> version = gs; drop keys
 //                               with gs - version > steps_to_live
 // Marking is one thread per slot; the kept slots are rehashed into a fresh
-// table (linear probing has no tombstones).  Rows of dropped keys are not
-// recycled ("TODO memory recycle" in the reference too).
+// table (linear probing has no tombstones).  Rows of dropped keys stay
+// allocated ("TODO memory recycle" in the reference too) until dr_ev_compact
+// moves the live rows above the live count into them (row compaction, below).
 // ---------------------------------------------------------------------------
 __global__ void ev_shrink_mark_kernel(Slot* __restrict__ slots, int64_t cap, const float* pool,
                                       const float* dflt, int64_t dim, int bf16,
@@ -3657,9 +3658,9 @@ int dr_ev_apply_adam(dr_ev* var, dr_ev* m, dr_ev* v, float beta1_power, float be
 // play the roles of the reference's RecordSparseIndices / IncrSave /
 // KvResourceIncrImport; the semantics are build-defined.
 // A key space that tracks updates holds one bit per row (EvShared::dirty).
-// Rows are never recycled and both growth and dr_ev_shrink keep a key's row,
-// so a bit stays with its key for the key's lifetime; the bit of an evicted
-// key stays set and selects nothing.
+// Growth and dr_ev_shrink keep a key's row and dr_ev_compact moves the bit
+// with the row, so a bit stays with its key for the key's lifetime; the bit
+// of an evicted key stays set and selects nothing until a compaction clears it.
 //   mark   : lane per key, the read-only probe of the primary column, atomicOr
 //   export : scan the cap + 1 slots (16-B loads, wave ballots, one append per
 //            block tile), radix sort on the sign-flipped key, gather
@@ -4035,6 +4036,280 @@ int dr_ev_upsert(dr_ev* ev, const int64_t* keys, int64_t n, const void* values,
   DR_HIP(hipFreeAsync(rows, st));
   DR_HIP(hipFreeAsync(init, st));
   post_call(s, st);
+  return DR_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Row compaction (dr_ev_compact): the rows of evicted keys are given back.
+// dr_ev_shrink leaves holes in [0, top); the live rows at or above the live
+// count L (movers) go into the holes below L, k-th smallest to k-th smallest,
+// and top becomes L.  Sources (>= L) and destinations (< L) are disjoint, so
+// the move is in place and parallel; no pool is copied and no pointer changes.
+//   live   : thread per slot (16-B load), atomicOr into a bitmap of top bits
+//   rank   : popcount per word, int32 exclusive scan (-> L), then thread per
+//            row: rank = scanned word base + popcount of the masked word;
+//            writes the ascending lists hole[k], mover[k]
+//   move   : G lanes per (k, column) copy the row; lane 0 of column 0 moves
+//            freq / version, writes remap[mover - L] = hole and clears the
+//            hole's stale dirty bit
+//   dirty  : a later launch ORs the movers' bits in at their new rows
+//   slots  : thread per slot, row >= L -> remap (bits 48..63 kept)
+//   tail   : freq / version [L, top) and the dirty bits of rows >= L zeroed
+//            (a new row relies on zeroed metadata), L stored to *top
+// ===========================================================================
+namespace dr {
+
+// the slot references a row: dr_ev_export's rule (occupied, published, live)
+__device__ __forceinline__ bool slot_has_row(const slot_v sv, bool special) {
+  const bool occupied = special ? sv.x == 0ull : sv.x != kEmptyKey;
+  return occupied && sv.y != kUnset && (sv.y & kRowMask) != kRowDead;
+}
+
+__global__ __launch_bounds__(256) void ev_compact_live_kernel(const Slot* __restrict__ slots,
+                                                              int64_t cap, int64_t top,
+                                                              uint32_t* __restrict__ live) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > cap) return;
+  const slot_v sv = gld(reinterpret_cast<const slot_v*>(slots + i));
+  if (!slot_has_row(sv, i == cap)) return;
+  const int64_t row = (int64_t)(sv.y & kRowMask);
+  if (row >= top) return;  // (never for a published row: keeps the bitmap in bounds)
+  // a row belongs to one key, so its bit is never found set: no load first
+  atomicOr(live + (row >> 5), 1u << (row & 31));
+}
+
+__global__ __launch_bounds__(256) void ev_compact_count_kernel(const uint32_t* __restrict__ live,
+                                                               int64_t nw,
+                                                               int32_t* __restrict__ cnt) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w < nw) cnt[w] = __popc(gld(live + w));
+}
+
+// pre[w] = live rows below row 32 * w; below = live rows below L.  Row r is
+// the (r - live rows below r)-th hole, or the (live rows below r - below)-th
+// mover: both lists come out ascending.
+__global__ __launch_bounds__(256) void ev_compact_rank_kernel(const uint32_t* __restrict__ live,
+                                                              const int32_t* __restrict__ pre,
+                                                              int64_t top, int64_t L, int32_t below,
+                                                              int32_t* __restrict__ holes,
+                                                              int32_t* __restrict__ movers) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= top) return;
+  const uint32_t lw = gld(live + (r >> 5));
+  const int b = (int)(r & 31);
+  const int32_t before = gld(pre + (r >> 5)) + __popc(lw & ((1u << b) - 1u));
+  const bool set = (lw >> b) & 1u;
+  if (r < L) {
+    if (!set) holes[r - before] = (int32_t)r;
+  } else if (set) {
+    movers[before - below] = (int32_t)r;
+  }
+}
+
+struct CompactCols {
+  float* pool[kMaxCols];
+  int32_t words[kMaxCols];  // float words per row
+  int32_t vec[kMaxCols];    // rows 16-B aligned: dwordx4 copies
+};
+
+template <int G>
+__global__ __launch_bounds__(256) void ev_compact_move_kernel(
+    CompactCols cc, const int32_t* __restrict__ holes, const int32_t* __restrict__ movers,
+    int64_t M, int64_t L, int64_t* __restrict__ freq, int64_t* __restrict__ version,
+    uint32_t* __restrict__ dirty, int32_t* __restrict__ remap) {
+  const int64_t k = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  if (k >= M) return;
+  const int c = blockIdx.y, lg = threadIdx.x % G;
+  const int64_t src = gld(movers + k), dst = gld(holes + k);
+  const int64_t w = cc.words[c];
+  ro_copy_row<G>(cc.pool[c] + src * w, cc.pool[c] + dst * w, w, cc.vec[c], lg);
+  if (c != 0 || lg != 0) return;
+  remap[src - L] = (int32_t)dst;
+  if (freq) freq[dst] = gld(freq + src);
+  if (version) version[dst] = gld(version + src);
+  if (dirty) {  // the evicted key's bit must not pass to the key that moves in
+    uint32_t* wd = dirty + (dst >> 5);
+    const uint32_t m = 1u << (dst & 31);
+    if (gld(wd) & m) atomicAnd(wd, ~m);
+  }
+}
+
+// after the move kernel: every hole's bit is clear, the movers' bits (rows
+// >= L, untouched so far) are still in place
+__global__ __launch_bounds__(256) void ev_compact_dirty_kernel(const int32_t* __restrict__ holes,
+                                                               const int32_t* __restrict__ movers,
+                                                               int64_t M,
+                                                               uint32_t* __restrict__ dirty) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= M) return;
+  const int64_t src = gld(movers + k), dst = gld(holes + k);
+  if ((gld(dirty + (src >> 5)) >> (src & 31)) & 1u) atomicOr(dirty + (dst >> 5), 1u << (dst & 31));
+}
+
+__global__ __launch_bounds__(256) void ev_compact_slots_kernel(Slot* __restrict__ slots,
+                                                               int64_t cap, int64_t L, int64_t top,
+                                                               const int32_t* __restrict__ remap) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > cap) return;
+  const slot_v sv = gld(reinterpret_cast<const slot_v*>(slots + i));
+  if (!slot_has_row(sv, i == cap)) return;
+  const int64_t row = (int64_t)(sv.y & kRowMask);
+  if (row < L || row >= top) return;
+  slots[i].rc = (sv.y & ~kRowMask) | (uint64_t)(uint32_t)gld(remap + (row - L));
+}
+
+__global__ __launch_bounds__(256) void ev_compact_tail_kernel(int64_t L, int64_t top,
+                                                              int64_t* __restrict__ freq,
+                                                              int64_t* __restrict__ version,
+                                                              uint32_t* __restrict__ dirty,
+                                                              int64_t* __restrict__ top_dev) {
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t r = L + t0; r < top; r += stride) {
+    if (freq) freq[r] = 0;
+    if (version) version[r] = 0;
+  }
+  if (dirty && top > L) {
+    const int64_t first = L >> 5, last = (top - 1) >> 5;
+    for (int64_t w = first + t0; w <= last; w += stride) {
+      if (w == first && (L & 31))
+        dirty[w] &= (1u << (L & 31)) - 1u;  // rows < L of the partly used word keep their bits
+      else
+        dirty[w] = 0u;
+    }
+  }
+  if (t0 == 0) *top_dev = L;
+}
+
+}  // namespace dr
+
+extern "C" {
+
+int dr_ev_rows_allocated(dr_ev* ev, int64_t* rows_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  DR_REQUIRE(ev && rows_host, DR_INVALID_ARGUMENT, "null argument");
+  DR_HIP(hipStreamSynchronize(dr::S(stream)));
+  DR_HIP(hipMemcpy(rows_host, ev->sh->top, sizeof(int64_t), hipMemcpyDeviceToHost));
+  return DR_OK;
+}
+
+int dr_ev_compact(dr_ev* ev, int64_t* reclaimed_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev, DR_INVALID_ARGUMENT, "null ev");
+  DR_REQUIRE(ev->col == 0, DR_INVALID_ARGUMENT, "compaction needs a primary EV");
+  EvShared* s = ev->sh;
+  hipStream_t st = S(stream);
+  if (reclaimed_host) *reclaimed_host = 0;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cs);
+  DR_REQUIRE(cs == hipStreamCaptureStatusNone, DR_INVALID_ARGUMENT,
+             "dr_ev_compact synchronises: not inside stream capture");
+  std::lock_guard<std::mutex> g(s->mu);
+  // kernels other streams enqueued on the rows must be done before they move
+  // (EvGuard keeps new ones from starting), as in grow()
+  DR_HIP(hipDeviceSynchronize());
+  int64_t top_before = 0;
+  DR_HIP(hipMemcpy(&top_before, s->top, sizeof(int64_t), hipMemcpyDeviceToHost));
+  // the counter passes row_cap when an insert ran out of rows (those keys
+  // hold kRowDead, not a row)
+  const int64_t top = std::min(top_before, s->row_cap);
+  DR_REQUIRE(top < ((int64_t)1 << 31), DR_INVALID_ARGUMENT,
+             "dr_ev_compact: %lld rows, the ranks are int32 (< 2^31)", (long long)top);
+  int64_t L = 0;
+  if (top > 0) {
+    const int64_t nw = ceil_div(top, 32);
+    const int64_t nslots = s->cap + 1;
+    Carver sz(nullptr);
+    sz.take<uint32_t>(nw);
+    sz.take<int32_t>(nw);
+    sz.take<int32_t>(nw);
+    sz.take<int64_t>(1);
+    sz.take<char>(scan_ws_bytes(nw));
+    DevBuf rank;
+    DR_HIP(rank.alloc(sz.used + 256, st));
+    Carver c(rank.p);
+    uint32_t* live = c.take<uint32_t>(nw);
+    int32_t* cnt = c.take<int32_t>(nw);
+    int32_t* pre = c.take<int32_t>(nw);
+    int64_t* total = c.take<int64_t>(1);
+    void* scan_ws = c.take<char>(scan_ws_bytes(nw));
+    int rc = fill_bytes(live, 0, (size_t)nw * sizeof(uint32_t), st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ev_compact_live_kernel, dim3((unsigned)ceil_div(nslots, 256)), dim3(256), 0,
+                       st, s->slots, s->cap, top, live);
+    hipLaunchKernelGGL(ev_compact_count_kernel, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st,
+                       live, nw, cnt);
+    DR_LAUNCH_CHECK();
+    rc = scan_exclusive_i32(cnt, pre, nw, nullptr, total, scan_ws, st);
+    if (rc) return rc;
+    DR_HIP(hipMemcpyAsync(&L, total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    DR_HIP(hipStreamSynchronize(st));
+    DR_REQUIRE(L >= 0 && L <= top, DR_INTERNAL, "dr_ev_compact: %lld live rows of %lld",
+               (long long)L, (long long)top);
+    if (L < top) {
+      // live rows below L: the word holding row L is inside the bitmap (L < top)
+      int32_t pre_l = 0;
+      uint32_t live_l = 0;
+      DR_HIP(hipMemcpyAsync(&pre_l, pre + (L >> 5), sizeof(pre_l), hipMemcpyDeviceToHost, st));
+      DR_HIP(hipMemcpyAsync(&live_l, live + (L >> 5), sizeof(live_l), hipMemcpyDeviceToHost, st));
+      DR_HIP(hipStreamSynchronize(st));
+      const int32_t below = pre_l + __builtin_popcount(live_l & ((1u << (L & 31)) - 1u));
+      const int64_t M = L - below;  // movers = holes below L
+      DR_REQUIRE(M >= 0 && M <= top - L, DR_INTERNAL, "dr_ev_compact: %lld movers, %lld rows above",
+                 (long long)M, (long long)(top - L));
+      DevBuf mv;
+      if (M > 0) {
+        Carver msz(nullptr);
+        msz.take<int32_t>(M);
+        msz.take<int32_t>(M);
+        msz.take<int32_t>(top - L);
+        DR_HIP(mv.alloc(msz.used + 256, st));
+        Carver mc(mv.p);
+        int32_t* holes = mc.take<int32_t>(M);
+        int32_t* movers = mc.take<int32_t>(M);
+        int32_t* remap = mc.take<int32_t>(top - L);
+        hipLaunchKernelGGL(ev_compact_rank_kernel, dim3((unsigned)ceil_div(top, 256)), dim3(256), 0,
+                           st, live, pre, top, L, below, holes, movers);
+        CompactCols cc;
+        memset(&cc, 0, sizeof(cc));
+        int ncols = 0;
+        for (int col = 0; col < kMaxCols; ++col) {
+          if (!s->pools[col]) continue;
+          const int64_t w = col_words(s, col);
+          cc.pool[ncols] = s->pools[col];
+          cc.words[ncols] = (int32_t)w;
+          cc.vec[ncols] = w % 4 == 0 && (uintptr_t)s->pools[col] % 16 == 0;
+          ++ncols;
+        }
+        constexpr int G = 16;
+        hipLaunchKernelGGL((ev_compact_move_kernel<G>),
+                           dim3((unsigned)ceil_div(M, 256 / G), (unsigned)ncols), dim3(256), 0, st,
+                           cc, holes, movers, M, L, s->freq, s->version, s->dirty, remap);
+        if (s->dirty)
+          hipLaunchKernelGGL(ev_compact_dirty_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256),
+                             0, st, holes, movers, M, s->dirty);
+        hipLaunchKernelGGL(ev_compact_slots_kernel, dim3((unsigned)ceil_div(nslots, 256)),
+                           dim3(256), 0, st, s->slots, s->cap, L, top, remap);
+        DR_LAUNCH_CHECK();
+      }
+      const int64_t blocks = std::min<int64_t>(std::max<int64_t>(ceil_div(top - L, 256), 1), 4096);
+      hipLaunchKernelGGL(ev_compact_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, st, L, top,
+                         s->freq, s->version, s->dirty, s->top);
+      DR_LAUNCH_CHECK();
+      DR_HIP(hipStreamSynchronize(st));  // the temporaries go with this call
+    }
+  }
+  // the device count is exact now, and a mirror issued before the call is stale
+  s->known = L;
+  s->adds_since_known = 0;
+  s->adds_since_copy = 0;
+  s->adds = s->copy_adds = EvShared::Streams();
+  s->copy_pending = false;
+  s->removed = 0;
+  if (reclaimed_host) *reclaimed_host = top - L;
   return DR_OK;
 }
 

@@ -201,6 +201,8 @@ SIGNATURES = {
     "dr_unique_i32_workspace_size": (_SZ, [_I64]),
     "dr_unique_i32": (_I32, [_P, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     "dr_ev_shrink": (_I32, [_P, _I64, _F32, _P, _P]),
+    "dr_ev_compact": (_I32, [_P, _P, _P]),
+    "dr_ev_rows_allocated": (_I32, [_P, _P, _P]),
     "dr_ev_reserve": (_I32, [_P, _I64, _P]),
     "dr_ev_resolve_workspace_size": (_SZ, [_I64]),
     "dr_ev_resolve": (_I32, [_P, _P, _I64, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -454,19 +454,27 @@ def write_ev_tensors(writer, tensor_key, offs, keys, vals, vers, frqs, suffix=""
     writer.add(pre + "freqs", frqs)
 
 
-def save(prefix, variables, global_step=None):
+def save(prefix, variables, global_step=None, compact=False):
     """Saver.save for EVs: {tensor_key: EmbeddingVariable} -> one bundle.
 
     Like DumpEv (save_restore_v2_ops.cc:117-133), each variable's key space
     is shrunk first (EmbeddingVar::Shrink: by L2 weight when the EV has an
     l2_weight_threshold, else by global step when steps_to_live > 0), so
-    evicted keys are not written; global_step None skips the step eviction."""
+    evicted keys are not written; global_step None skips the step eviction.
+
+    compact=True also gives the evicted keys' rows back (EmbeddingVariable.
+    compact): each distinct key space once, after its shrink and before its
+    first dump.  The bundle's bytes do not depend on it."""
     w = BundleWriter(prefix)
+    compacted = set()
     for name in variables:
         ev = variables[name]
         p = ev._primary or ev
         if p.l2_weight_threshold != -1.0 or (global_step is not None and p.steps_to_live > 0):
             ev.shrink(0 if global_step is None else global_step)
+        if compact and id(p) not in compacted:
+            compacted.add(id(p))
+            p.compact()
         dump_embedding_values(ev, name, w)
     w.finish()
     return prefix

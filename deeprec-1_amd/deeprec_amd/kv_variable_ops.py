@@ -646,6 +646,30 @@ class EmbeddingVariable(object):
                                  stream_handle(self.device)))
         return n.value
 
+    def compact(self):
+        """Row compaction (dr_ev_compact) of the key space this EV shares with
+        its slots: the live rows above the live count move into the rows that
+        shrink() left behind and the tail is free for new keys.  Returns the
+        rows reclaimed.  Row indices handed out earlier are invalid afterwards,
+        so a queued gradient (pending_grads of the primary or a slot EV: it
+        may hold a forward's recorded rows) is refused: apply it first."""
+        p = self._primary or self
+        for ev in [p] + list(p._slots.values()):
+            if ev.pending_grads:
+                raise _lib.InvalidArgumentError(
+                    _lib.INVALID_ARGUMENT, "compact: %s has %d pending gradient(s), which may "
+                    "hold row indices; apply_gradients first" % (ev.name, len(ev.pending_grads)))
+        n = C.c_int64(0)
+        check(lib().dr_ev_compact(p._h, C.byref(n), stream_handle(self.device)))
+        return n.value
+
+    def rows_allocated(self):
+        """Rows allocated in the key space (the device row counter):
+        total_count()[0] plus the rows of evicted keys not yet compacted."""
+        n = C.c_int64(0)
+        check(lib().dr_ev_rows_allocated(self._h, C.byref(n), stream_handle(self.device)))
+        return n.value
+
 
 def mark_updated_grouped(evs, keys, num_valid=None):
     """mark_updated over several EVs with one launch per device and

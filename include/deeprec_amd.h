@@ -390,6 +390,39 @@ int dr_ev_size(dr_ev* ev, int64_t* size_host, void* stream);
 /* *removed_host (nullable) = keys dropped.                                   */
 int dr_ev_shrink(dr_ev* ev, int64_t global_step, float l2_weight_threshold,
                  int64_t* removed_host, void* stream);
+/* Row compaction of a key space (a primary EV and its slot EVs): gives the  */
+/* rows of evicted keys back.  dr_ev_shrink drops keys from the slot table   */
+/* and leaves their rows allocated; this call moves the live rows that lie   */
+/* above the live count into the holes below it and lowers the device row    */
+/* counter to the live count, so new keys reuse the tail.  With `top` the    */
+/* row counter at entry, a row r < top is LIVE when a published slot         */
+/* references it (occupied, row assigned and not dead; the key -1 slot       */
+/* counts), otherwise a HOLE; L = live rows; a MOVER is a live row >= L.     */
+/* After the call: live rows < L keep their index; the k-th smallest mover   */
+/* has taken the k-th smallest hole < L (ascending against ascending);       */
+/* the row counter is L; *reclaimed_host (nullable) = top - L.  A moved row  */
+/* goes bitwise in every column that exists (float, double, bf16), with its  */
+/* freq / version where kept and its update-tracking bit where tracking is   */
+/* on: a bit moves with its key, the bits of holes and of the tail are       */
+/* cleared, freq / version of rows [L, top) are zeroed (new rows rely on     */
+/* that).  Only bits 0..47 of the moved keys' slot words change: keys, slot  */
+/* positions, the table, every pool / freq / version / bitmap pointer and    */
+/* dr_ev_row_capacity stay, so a captured step stays valid across the call   */
+/* (not so across dr_ev_shrink or a growth).  dr_ev_size, dr_ev_export,      */
+/* dr_ev_export_updated, every gather / find / read-only lookup,             */
+/* dr_ev_key_meta and the Bloom counters give what they gave before.         */
+/* ROW INDICES HANDED OUT BEFORE THE CALL ARE INVALID AFTER IT: the rows of  */
+/* dr_ev_resolve* / dr_ev_find_grouped, a forward's recorded rows            */
+/* (dr_ev_lookup_onehot_rows) and anything derived from them -- apply them   */
+/* first.  Primary EVs only; refused inside stream capture; needs            */
+/* top < 2^31 (int32 ranks).  Synchronises the device before it reads and    */
+/* the stream before it returns; temporaries come from the stream's memory   */
+/* pool.  With no hole it changes nothing; with holes only above L it only   */
+/* lowers the counter and resets the tail.                                   */
+int dr_ev_compact(dr_ev* ev, int64_t* reclaimed_host /* nullable */, void* stream);
+/* Rows allocated in the EV's key space (the device row counter): the keys   */
+/* of dr_ev_size plus the rows of evicted keys not yet compacted.  Syncs.    */
+int dr_ev_rows_allocated(dr_ev* ev, int64_t* rows_host, void* stream);
 int64_t dr_ev_dim(dr_ev* ev);
 /* filter_freq of the EV's Counter / Bloom admission filter (0: none).        */
 int64_t dr_ev_filter_freq(dr_ev* ev);
@@ -566,8 +599,9 @@ int dr_ev_export(dr_ev* ev, int64_t* keys_out, float* values_out, int64_t* versi
 /* kv_variable_ops.cc:719-783); the semantics below are build-defined.      */
 /* A primary EV and its slot EVs share one key space, and tracking is a     */
 /* property of that key space: one bit per row, ceil(row_capacity / 32)     */
-/* uint32 words, present only while tracking is on.  Rows are never         */
-/* recycled, so a bit stays with its key across growth and dr_ev_shrink.    */
+/* uint32 words, present only while tracking is on.  A bit stays with its   */
+/* key: growth and dr_ev_shrink keep a key's row, and dr_ev_compact moves   */
+/* the bit with the row (and clears the bits of evicted keys' rows).        */
 /* int64 keys only.                                                         */
 /* ------------------------------------------------------------------------ */
 /* on != 0: allocate and zero the bitmap; on == 0: free it.  Idempotent;    */
@@ -590,8 +624,8 @@ int dr_ev_mark_updated(dr_ev* const* evs, int num_tables, const int64_t* keys,
                        const int64_t* koff_host, const int64_t* const* n_dev_per_table,
                        void* stream);
 /* Number of marked rows: an UPPER BOUND on what dr_ev_export_updated       */
-/* returns (rows of evicted keys and rows whose column is untouched still   */
-/* count).  Syncs.                                                          */
+/* returns (rows of evicted keys -- until dr_ev_compact clears their bits -- */
+/* and rows whose column is untouched still count).  Syncs.                 */
 int dr_ev_updated_count(dr_ev* ev, int64_t* bound_host, void* stream);
 /* The entries of dr_ev_export whose row is marked, with dr_ev_export's     */
 /* contract: NULL outputs query the count into *m_host, capacity < m is     */
