@@ -19,6 +19,8 @@
 //   freq/version    [row_cap] int64, only when filter / steps_to_live on.
 //   dirty           [ceil(row_cap / 32)] uint32, one bit per row, only while update
 //                   tracking is on (incremental checkpoints, below).
+//   rm_log          int64 keys dropped by shrink / remove, only while the removal
+//                   log is on (keyed removal, below).
 // A key owns one row id for all columns; a column's row is initialised from
 // that column's default the first time it is touched, exactly like the
 // reference's lazily allocated per-emb_index rows.
@@ -94,7 +96,12 @@ struct EvShared {
   bool copy_exact = false;
   hipEvent_t copy_ev = nullptr;
   int64_t* pinned_top = nullptr;
-  int64_t removed = 0;  // keys removed by dr_ev_shrink whose rows dr_ev_compact has not reclaimed
+  // keys removed by dr_ev_shrink / dr_ev_remove whose rows dr_ev_compact has not reclaimed
+  int64_t removed = 0;
+  // removal log (dr_ev_track_removals): the keys shrink / remove dropped, rm_n of
+  // rm_cap int64 entries used (host counts); nullptr while the log is off
+  int64_t* rm_log = nullptr;
+  int64_t rm_n = 0, rm_cap = 0;
   // value dtype: 1 = float, 2 = double (a double row is stored as 2 * dim
   // float words and moved bitwise; `dim` counts float words)
   int value_words = 1;
@@ -1230,6 +1237,12 @@ __global__ void ev_rehash_kept_kernel(const Slot* __restrict__ old_slots, int64_
   }
 }
 
+// Removal log (keyed removal section, below): appends the keys of the slots a
+// mark step dropped (keep == 0) while the old slot table is still there.
+// `cnt` is a device counter the caller owns; synchronises.
+static int log_dropped(EvShared* s, const uint8_t* keep, int64_t dropped, unsigned long long* cnt,
+                       hipStream_t st);
+
 // ---------------------------------------------------------------------------
 // Rehash into a larger slot table (growth).
 // ---------------------------------------------------------------------------
@@ -1334,6 +1347,7 @@ static void free_shared(EvShared* s) {
   (void)hipFree(s->freq);
   (void)hipFree(s->version);
   (void)hipFree(s->dirty);
+  (void)hipFree(s->rm_log);
   for (int c = 0; c < kMaxCols; ++c) {
     (void)hipFree(s->pools[c]);
     (void)hipFree(s->defaults[c]);
@@ -2953,6 +2967,7 @@ int dr_ev_shrink(dr_ev* ev, int64_t global_step, float l2_weight_threshold,
         hipMemcpy(&removed, cnt, sizeof(removed), hipMemcpyDeviceToHost) != hipSuccess)
       rc = DR_INTERNAL;
   }
+  if (s->rm_log && !rc) rc = log_dropped(s, keep, (int64_t)removed, cnt, st);
   (void)hipFree(keep);
   (void)hipFree(cnt);
   if (rc) {
@@ -4310,6 +4325,351 @@ int dr_ev_compact(dr_ev* ev, int64_t* reclaimed_host, void* stream) {
   s->copy_pending = false;
   s->removed = 0;
   if (reclaimed_host) *reclaimed_host = top - L;
+  return DR_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Keyed removal (dr_ev_remove) and the removal log (dr_ev_track_removals):
+// how a delta carries evictions.  Removal is shrink with
+// the key list as the selection rule: mark the doomed slots in `keep`, rehash
+// the kept slots into a fresh table (ev_rehash_kept_kernel, unchanged), swap.
+//   mark    : lane per key, the plain-load probe walk yielding the SLOT INDEX;
+//             a hit clears its byte of `keep` with an atomic AND on the word
+//             that holds it, and the lane that finds the byte still set -- the
+//             first of any duplicates -- counts the key (one add per block tile)
+//   collect : only while the log is on, after the mark step of shrink / remove
+//             and before the old table goes: scans the cap + 1 keep bytes, loads
+//             the key of a dropped slot (-1 for the slot at cap), one reservation
+//             per block tile in the log
+//   export  : sign-flip copy of the log, radix sort, head flags, exclusive
+//             scan, scatter of the distinct keys
+// ===========================================================================
+namespace dr {
+
+static constexpr int64_t kRmLogInit = 1024;  // first size of the removal log, int64 entries
+
+// Slot index of `key` when it is in the map, published and live, else -1: the
+// walk of ev_probe_row without the column test.
+__device__ __forceinline__ int64_t ev_probe_slot_index(const Slot* __restrict__ slots, int64_t cap,
+                                                       uint64_t key) {
+  if (key == kEmptyKey) {
+    const slot_v sv = gld(reinterpret_cast<const slot_v*>(slots + cap));
+    return slot_has_row(sv, true) ? cap : -1;
+  }
+  const uint64_t mask = (uint64_t)cap - 1;
+  const uint64_t h0 = mix64(key) & mask;
+  for (int64_t probes = 0; probes <= cap; ++probes) {
+    const int64_t idx = (int64_t)probe_slot(h0, (uint64_t)probes, mask);
+    const slot_v sv = gld(reinterpret_cast<const slot_v*>(slots + idx));
+    if (sv.x == key) return slot_has_row(sv, false) ? idx : -1;
+    if (sv.x == kEmptyKey) return -1;
+  }
+  return -1;
+}
+
+// keep: (cap + 1) bytes, all 1 at entry, addressed as uint32 words (the
+// allocation is rounded up to whole words).  A block takes a tile of
+// 256 * kRmMarkItems keys and adds its first flippers to the one counter with
+// ONE atomic (wave ballots, wave totals in LDS): an add per wave serialises
+// on the counter, as the scan of the update tracking found.
+static constexpr int kRmMarkItems = 8;
+
+__global__ __launch_bounds__(256) void ev_remove_mark_kernel(
+    const Slot* __restrict__ slots, int64_t cap, const int64_t* __restrict__ keys, int64_t n,
+    uint32_t* __restrict__ keep_words, unsigned long long* __restrict__ nremoved) {
+  __shared__ unsigned wtot[4];
+  const int64_t tile = (int64_t)blockIdx.x * (256 * kRmMarkItems);
+  unsigned mine = 0;  // wave-uniform
+#pragma unroll
+  for (int j = 0; j < kRmMarkItems; ++j) {
+    const int64_t i = tile + j * 256 + threadIdx.x;
+    bool first = false;
+    if (i < n) {
+      const int64_t idx = ev_probe_slot_index(slots, cap, (uint64_t)gld(keys + i));
+      if (idx >= 0) {
+        const uint32_t m = 0xFFu << (8 * (int)(idx & 3));
+        first = (atomicAnd(keep_words + (idx >> 2), ~m) & m) != 0u;
+      }
+    }
+    mine += (unsigned)__popcll(__ballot(first));
+  }
+  if (lane_id() == 0) wtot[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    if (t) atomicAdd(nremoved, (unsigned long long)t);
+  }
+}
+
+// Appends the keys of the slots with keep == 0 to log[0, room): a block takes a
+// tile of 256 * kRmItems slots, counts its hits (wave ballots, wave totals in
+// LDS) and reserves their places with one atomic add (ev_scan_updated_kernel's
+// scheme).  The slot's key is loaded only for a hit.
+static constexpr int kRmItems = 8;
+
+__global__ __launch_bounds__(256) void ev_collect_dropped_kernel(
+    const Slot* __restrict__ slots, int64_t cap, const uint8_t* __restrict__ keep,
+    int64_t* __restrict__ log, int64_t room, unsigned long long* __restrict__ count) {
+  __shared__ unsigned wtot[4];
+  __shared__ unsigned long long sbase;
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t tile = (int64_t)blockIdx.x * (256 * kRmItems);
+  uint64_t mask[kRmItems];  // wave-uniform
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < kRmItems; ++j) {
+    const int64_t i = tile + j * 256 + threadIdx.x;
+    mask[j] = __ballot(i <= cap && gld(keep + i) == 0);
+    mine += (unsigned)__popcll(mask[j]);
+  }
+  if (lane == 0) wtot[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    sbase = t ? atomicAdd(count, (unsigned long long)t) : 0ull;
+  }
+  __syncthreads();
+  int64_t pos = (int64_t)sbase;
+  for (int w = 0; w < wave; ++w) pos += wtot[w];
+#pragma unroll
+  for (int j = 0; j < kRmItems; ++j) {
+    if ((mask[j] >> lane) & 1ull) {
+      const int64_t i = tile + j * 256 + threadIdx.x;
+      const int64_t p = pos + __popcll(mask[j] & lanemask_lt());
+      if (p < room) log[p] = i < cap ? (int64_t)gld(&slots[i].key) : -1;
+    }
+    pos += __popcll(mask[j]);
+  }
+}
+
+__global__ __launch_bounds__(256) void ev_removed_flip_kernel(const int64_t* __restrict__ log,
+                                                              int64_t m, uint64_t* __restrict__ k,
+                                                              int32_t* __restrict__ idx) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  k[i] = (uint64_t)gld(log + i) ^ (1ull << 63);
+  idx[i] = (int32_t)i;
+}
+
+// head[i] = 1 where the sorted key differs from its predecessor
+__global__ __launch_bounds__(256) void ev_removed_heads_kernel(const uint64_t* __restrict__ ks,
+                                                               int64_t m,
+                                                               int32_t* __restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  head[i] = (i == 0 || gld(ks + i) != gld(ks + i - 1)) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void ev_removed_emit_kernel(const uint64_t* __restrict__ ks,
+                                                              const int32_t* __restrict__ head,
+                                                              const int32_t* __restrict__ pre,
+                                                              int64_t m, int64_t capacity,
+                                                              int64_t* __restrict__ keys_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m || !gld(head + i)) return;
+  const int64_t p = gld(pre + i);
+  if (p < capacity) keys_out[p] = (int64_t)(gld(ks + i) ^ (1ull << 63));
+}
+
+static int log_dropped(EvShared* s, const uint8_t* keep, int64_t dropped, unsigned long long* cnt,
+                       hipStream_t st) {
+  if (dropped <= 0) return DR_OK;
+  const int64_t need = s->rm_n + dropped;
+  if (need > s->rm_cap) {  // geometric growth; grow()'s rule: synchronise, then free
+    int64_t ncap = std::max<int64_t>(s->rm_cap, kRmLogInit);
+    while (ncap < need) ncap *= 2;
+    int64_t* nl = nullptr;
+    DR_HIP(hipMalloc(&nl, (size_t)ncap * sizeof(int64_t)));
+    if ((s->rm_n && hipMemcpyAsync(nl, s->rm_log, (size_t)s->rm_n * sizeof(int64_t),
+                                   hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      (void)hipFree(nl);
+      set_error("removal log: growing to %lld entries failed", (long long)ncap);
+      return DR_INTERNAL;
+    }
+    (void)hipFree(s->rm_log);
+    s->rm_log = nl;
+    s->rm_cap = ncap;
+  }
+  int rc = fill_bytes(cnt, 0, sizeof(unsigned long long), st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ev_collect_dropped_kernel,
+                     dim3((unsigned)ceil_div(s->cap + 1, 256 * kRmItems)), dim3(256), 0, st,
+                     s->slots, s->cap, keep, s->rm_log + s->rm_n, s->rm_cap - s->rm_n, cnt);
+  DR_LAUNCH_CHECK();
+  unsigned long long got = 0;
+  DR_HIP(hipMemcpyAsync(&got, cnt, sizeof(got), hipMemcpyDeviceToHost, st));
+  DR_HIP(hipStreamSynchronize(st));
+  DR_REQUIRE((int64_t)got == dropped, DR_INTERNAL, "removal log: %lld keys collected of %lld dropped",
+             (long long)got, (long long)dropped);
+  s->rm_n = need;
+  return DR_OK;
+}
+
+}  // namespace dr
+
+extern "C" {
+
+int dr_ev_remove(dr_ev* ev, const int64_t* keys, int64_t n, int64_t* removed_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && ev->col == 0, DR_INVALID_ARGUMENT, "remove needs a primary EV");
+  DR_REQUIRE(n >= 0 && (n == 0 || keys), DR_INVALID_ARGUMENT, "bad argument");
+  EvShared* s = ev->sh;
+  hipStream_t st = S(stream);
+  if (removed_host) *removed_host = 0;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cs);
+  DR_REQUIRE(cs == hipStreamCaptureStatusNone, DR_INVALID_ARGUMENT,
+             "dr_ev_remove synchronises: not inside stream capture");
+  if (n == 0) return DR_OK;
+  std::lock_guard<std::mutex> g(s->mu);
+  const int64_t ns_ = s->cap + 1;
+  const size_t keep_bytes = (size_t)ceil_div(ns_, 4) * 4;  // whole words for the atomic AND
+  uint8_t* keep = nullptr;
+  unsigned long long* cnt = nullptr;
+  Slot* ns = nullptr;
+  DR_HIP(hipMalloc(&keep, keep_bytes));
+  if (hipMalloc(&cnt, sizeof(unsigned long long)) != hipSuccess) {
+    (void)hipFree(keep);
+    DR_REQUIRE(false, DR_RESOURCE_EXHAUSTED, "remove: out of device memory");
+  }
+  if (hipMalloc(&ns, (size_t)ns_ * sizeof(Slot)) != hipSuccess) {
+    (void)hipFree(keep);
+    (void)hipFree(cnt);
+    DR_REQUIRE(false, DR_RESOURCE_EXHAUSTED, "remove: out of device memory");
+  }
+  int rc = fill_bytes(cnt, 0, sizeof(unsigned long long), st);
+  if (!rc) rc = fill_bytes(keep, 1, keep_bytes, st);
+  if (!rc) rc = fill_bytes(ns, 0xFF, (size_t)ns_ * sizeof(Slot), st);
+  unsigned long long removed = 0;
+  if (!rc) {
+    hipLaunchKernelGGL(ev_remove_mark_kernel,
+                       dim3((unsigned)ceil_div(n, 256 * kRmMarkItems)), dim3(256), 0, st,
+                       s->slots, s->cap, keys, n, reinterpret_cast<uint32_t*>(keep), cnt);
+    hipLaunchKernelGGL(ev_rehash_kept_kernel, dim3((unsigned)ceil_div(ns_, 256)), dim3(256), 0, st,
+                       s->slots, s->cap, keep, ns);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+        hipMemcpy(&removed, cnt, sizeof(removed), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = DR_INTERNAL;
+  }
+  if (s->rm_log && !rc) rc = log_dropped(s, keep, (int64_t)removed, cnt, st);
+  (void)hipFree(keep);
+  (void)hipFree(cnt);
+  if (rc) {
+    (void)hipFree(ns);
+    set_error("dr_ev_remove failed");
+    return rc;
+  }
+  (void)hipFree(s->slots);
+  s->slots = ns;
+  s->removed += (int64_t)removed;
+  if (removed_host) *removed_host = (int64_t)removed;
+  return DR_OK;
+}
+
+int dr_ev_track_removals(dr_ev* ev, int on, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev, DR_INVALID_ARGUMENT, "null ev");
+  EvShared* s = ev->sh;
+  std::lock_guard<std::mutex> g(s->mu);
+  if (on) {
+    if (s->rm_log) return DR_OK;
+    DR_HIP(hipMalloc(&s->rm_log, (size_t)kRmLogInit * sizeof(int64_t)));
+    s->rm_cap = kRmLogInit;
+    s->rm_n = 0;
+    return DR_OK;
+  }
+  if (!s->rm_log) return DR_OK;
+  DR_HIP(hipStreamSynchronize(S(stream)));
+  DR_HIP(hipFree(s->rm_log));
+  s->rm_log = nullptr;
+  s->rm_n = s->rm_cap = 0;
+  return DR_OK;
+}
+
+int dr_ev_tracking_removals(dr_ev* ev) { return ev ? (ev->sh->rm_log ? 1 : 0) : -1; }
+
+int dr_ev_removed_count(dr_ev* ev, int64_t* n_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  (void)stream;
+  DR_REQUIRE(ev && n_host, DR_INVALID_ARGUMENT, "null argument");
+  DR_REQUIRE(ev->sh->rm_log, DR_INVALID_ARGUMENT, "the EV's key space is not logging removals");
+  std::lock_guard<std::mutex> g(ev->sh->mu);
+  *n_host = ev->sh->rm_n;
+  return DR_OK;
+}
+
+int dr_ev_clear_removed(dr_ev* ev, void* stream) {
+  dr::EvGuard guard_(ev);
+  (void)stream;
+  DR_REQUIRE(ev, DR_INVALID_ARGUMENT, "null ev");
+  DR_REQUIRE(ev->sh->rm_log, DR_INVALID_ARGUMENT, "the EV's key space is not logging removals");
+  std::lock_guard<std::mutex> g(ev->sh->mu);
+  ev->sh->rm_n = 0;
+  return DR_OK;
+}
+
+int dr_ev_export_removed(dr_ev* ev, int64_t* keys_out, int64_t capacity, int64_t* m_host,
+                         void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && m_host, DR_INVALID_ARGUMENT, "null argument");
+  EvShared* s = ev->sh;
+  DR_REQUIRE(s->rm_log, DR_INVALID_ARGUMENT, "the EV's key space is not logging removals");
+  hipStream_t st = S(stream);
+  std::lock_guard<std::mutex> g(s->mu);
+  *m_host = 0;
+  const int64_t m = s->rm_n;
+  if (m == 0) return DR_OK;
+  DR_REQUIRE(m < ((int64_t)1 << 31), DR_INVALID_ARGUMENT,
+             "dr_ev_export_removed: %lld log entries, the sort takes < 2^31", (long long)m);
+  const size_t sort_ws = dr_sort_pairs_workspace_size(m);
+  Carver sz(nullptr);
+  sz.take<uint64_t>(m);
+  sz.take<int32_t>(m);
+  sz.take<uint64_t>(m);
+  sz.take<int32_t>(m);
+  sz.take<int32_t>(m);
+  sz.take<int32_t>(m);
+  sz.take<int64_t>(1);
+  sz.take<char>(sort_ws);
+  sz.take<char>(scan_ws_bytes(m));
+  DevBuf buf;
+  DR_HIP(buf.alloc(sz.used + 256, st));
+  Carver c(buf.p);
+  uint64_t* kbuf = c.take<uint64_t>(m);
+  int32_t* ibuf = c.take<int32_t>(m);
+  uint64_t* ksorted = c.take<uint64_t>(m);
+  int32_t* isorted = c.take<int32_t>(m);
+  int32_t* head = c.take<int32_t>(m);
+  int32_t* pre = c.take<int32_t>(m);
+  int64_t* total = c.take<int64_t>(1);
+  char* ws = c.take<char>(sort_ws);
+  void* scan_ws = c.take<char>(scan_ws_bytes(m));
+  const dim3 grid((unsigned)ceil_div(m, 256));
+  hipLaunchKernelGGL(ev_removed_flip_kernel, grid, dim3(256), 0, st, s->rm_log, m, kbuf, ibuf);
+  DR_LAUNCH_CHECK();
+  int rc = dr_sort_pairs(kbuf, ibuf, ksorted, isorted, m, 0, 64, ws, sort_ws, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ev_removed_heads_kernel, grid, dim3(256), 0, st, ksorted, m, head);
+  DR_LAUNCH_CHECK();
+  rc = scan_exclusive_i32(head, pre, m, nullptr, total, scan_ws, st);
+  if (rc) return rc;
+  int64_t distinct = 0;
+  DR_HIP(hipMemcpyAsync(&distinct, total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DR_HIP(hipStreamSynchronize(st));
+  *m_host = distinct;
+  if (!keys_out) return DR_OK;
+  DR_REQUIRE(capacity >= distinct, DR_INVALID_ARGUMENT, "export capacity %lld < %lld",
+             (long long)capacity, (long long)distinct);
+  hipLaunchKernelGGL(ev_removed_emit_kernel, grid, dim3(256), 0, st, ksorted, head, pre, m,
+                     capacity, keys_out);
+  DR_LAUNCH_CHECK();
+  DR_HIP(hipStreamSynchronize(st));  // the temporaries go with this call
   return DR_OK;
 }
 

@@ -239,6 +239,12 @@ SIGNATURES = {
     "dr_ev_export_updated": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P]),
     "dr_ev_clear_updated": (_I32, [_P, _P]),
     "dr_ev_upsert": (_I32, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _P]),
+    "dr_ev_remove": (_I32, [_P, _P, _I64, _P, _P]),
+    "dr_ev_track_removals": (_I32, [_P, _I32, _P]),
+    "dr_ev_tracking_removals": (_I32, [_P]),
+    "dr_ev_removed_count": (_I32, [_P, _P, _P]),
+    "dr_ev_export_removed": (_I32, [_P, _P, _I64, _P, _P]),
+    "dr_ev_clear_removed": (_I32, [_P, _P]),
     "dr_ev_key_meta": (_I32, [_P, _P, _I64, _P, _P, _P, _P]),
     "dr_ev_apply_sgd": (_I32, [_P, _F32, _P, _P, _I64, _P, _I64, _P]),
     "dr_ev_apply_adagrad": (_I32, [_P, _P, _F32, _P, _P, _I64, _P, _I64, _P]),

@@ -433,6 +433,20 @@ def partition_snapshot(keys, values, versions, freqs):
     return offs, ks, vals, versions, freqs
 
 
+def partition_keys(keys):
+    """partition_snapshot's rule for a bare key list (a delta's removed
+    keys): negative keys dropped, the rest grouped by key % 1000 (stable).
+    Returns (offsets int32 [1001], keys) as device tensors."""
+    from . import ops
+    keys = keys[keys >= 0]
+    offs = torch.zeros(SAVED_PARTITION_NUM + 1, dtype=torch.int32, device=keys.device)
+    if keys.numel() == 0:
+        return offs, keys
+    ks, _, counts = ops.partition_by_owner(keys.contiguous(), SAVED_PARTITION_NUM)
+    offs[1:] = torch.cumsum(counts[:SAVED_PARTITION_NUM], 0).to(torch.int32)
+    return offs, ks
+
+
 def dump_embedding_values(ev, tensor_key, writer):
     """DumpEmbeddingValues (kv_variable_ops.h:148-265) of one EV (primary or
     slot) under `tensor_key` (e.g. "emb/part_0")."""
@@ -568,32 +582,91 @@ def save_incremental(prefix, variables, global_step=None):
     grouped by key % 1000, negative keys dropped, versions / freqs empty when
     the EV keeps none.  Every key space must be tracking (track_updates()).
     Each distinct key space is cleared once, after all of its columns are
-    written.  Nothing is shrunk -- eviction stays with the full save -- and
-    a delta does not carry evictions: an evicted key is simply absent from
-    it, so a replica drops it at its next full restore.  `global_step` is
-    accepted for symmetry with save() and unused.  Returns `prefix`."""
+    written.
+
+    Evictions: with `global_step` given, a key space whose primary has
+    steps_to_live > 0 or an l2_weight_threshold is shrunk first, exactly as
+    save() does (global_step None shrinks nothing: eviction then stays with
+    the full save).  A key space that logs removals (track_removals()) also
+    gets, under its PRIMARY's tensor key and after that name's five tensors,
+    NAME-sparse_incr_removed_partition_offset (int32 [1001]) and
+    NAME-sparse_incr_removed_keys: the distinct keys shrink() / remove()
+    dropped since the log was last cleared, negative keys dropped and the
+    rest grouped by key % 1000; the log is cleared with the marks.  The
+    primary of such a key space must be among `variables`.  A key space that
+    does not log removals gets neither tensor and its delta carries no
+    evictions: an evicted key is simply absent from it, and a replica drops
+    it at its next full restore.  Returns `prefix`."""
     w = BundleWriter(prefix)
     spaces = {}
+    for ev in variables.values():
+        p = ev._primary or ev
+        if id(p) in spaces:
+            continue
+        spaces[id(p)] = p
+        if p.tracking_removals() and not any(v is p for v in variables.values()):
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "save_incremental: %s logs removals, which are written "
+                "under the primary's tensor key: name it in `variables`" % p.name)
+        if global_step is not None and (p.l2_weight_threshold != -1.0 or p.steps_to_live > 0):
+            p.shrink(global_step)
     for name in variables:
         ev = variables[name]
         keys, vals, vers, frqs = ev.export_updated()
         offs, keys, vals, vers, frqs = partition_snapshot(keys, vals, vers, frqs)
         write_ev_tensors(w, name, offs, keys, vals.reshape(-1, ev.dim), vers, frqs, INCR_SUFFIX)
-        p = ev._primary or ev
-        spaces[id(p)] = p
+        if ev._primary is None and ev.tracking_removals():
+            offs, keys = partition_keys(ev.export_removed())
+            w.add(name + "-" + INCR_SUFFIX + "removed_partition_offset", offs)
+            w.add(name + "-" + INCR_SUFFIX + "removed_keys", keys)
     w.finish()
     for p in spaces.values():
         p.clear_updated()
+        if p.tracking_removals():
+            p.clear_removed()
     return prefix
 
 
-def restore_incremental(prefix, variables, partition_id=0, partition_num=1):
+def restore_incremental(prefix, variables, partition_id=0, partition_num=1, compact=False):
     """KvResourceIncrImport's role: apply a delta written by save_incremental
-    to {tensor_key: EmbeddingVariable}.  The walk of restore() (parts,
-    sub-partitions, the key % 1000 % partition_num filter) over the
-    NAME-sparse_incr_* tensors, ending in upsert: rows of keys already
-    present are overwritten, new keys are created."""
+    to {tensor_key: EmbeddingVariable}, in two passes.  First the delta's
+    removals: for every primary whose name has NAME-sparse_incr_removed_keys
+    in the bundle (every saved part of a partitioned name), remove() those
+    keys, once per key space and without a partition filter -- absent keys
+    are ignored.  Then the walk of restore() (parts, sub-partitions, the
+    key % 1000 % partition_num filter) over the NAME-sparse_incr_* tensors,
+    ending in upsert: rows of keys already present are overwritten, new keys
+    are created.  Removals first, upserts second: a key that was evicted,
+    re-created and updated again ends with its new row, and one that was
+    re-created but never updated ends absent, so the replica serves the
+    default as the trainer's fresh row does.  compact=True compacts each
+    distinct key space once at the end (EmbeddingVariable.compact), which is
+    what keeps a replica fed by deltas alone bounded.  A delta without the
+    removed_* tensors restores as before."""
     r = BundleReader(prefix)
+    sfx = "-" + INCR_SUFFIX + "removed_keys"
+    for name in variables:
+        ev = variables[name]
+        if ev._primary is not None:
+            continue
+        if "part_" not in name:
+            tnames = [name]
+        else:
+            tnames, part = [], 0
+            while r.contains(_part_name(name, part, partition_id) + "-" + INCR_SUFFIX + "keys"):
+                tnames.append(_part_name(name, part, partition_id))
+                part += 1
+        gone = [r.lookup(t + sfx) for t in tnames if r.contains(t + sfx)]
+        gone = [g for g in gone if g.size]
+        if gone:
+            ev.remove(torch.as_tensor(np.concatenate(gone), device=ev.device))
     for name in variables:
         restore_embedding_variable(variables[name], r, name, partition_id, partition_num,
                                    INCR_SUFFIX, True)
+    if compact:
+        done = set()
+        for ev in variables.values():
+            p = ev._primary or ev
+            if id(p) not in done:
+                done.add(id(p))
+                p.compact()

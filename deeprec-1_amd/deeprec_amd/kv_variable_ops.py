@@ -670,6 +670,58 @@ class EmbeddingVariable(object):
         check(lib().dr_ev_rows_allocated(self._h, C.byref(n), stream_handle(self.device)))
         return n.value
 
+    # -- keyed removal and the removal log (build-defined) --
+    def remove(self, keys):
+        """Remove `keys` from the key space this EV shares with its slots
+        (dr_ev_remove, through the primary as shrink()).  Absent keys are
+        ignored, duplicates count once; returns the distinct keys removed.
+        Rows stay allocated until compact().  A call costs one pass over the
+        slot table whatever len(keys) is: batch.  A queued gradient
+        (pending_grads of the primary or a slot EV) is refused, as in
+        compact(): its recorded rows would refer to dead keys."""
+        self._require_int64_keys("remove")
+        p = self._primary or self
+        for ev in [p] + list(p._slots.values()):
+            if ev.pending_grads:
+                raise _lib.InvalidArgumentError(
+                    _lib.INVALID_ARGUMENT, "remove: %s has %d pending gradient(s), which may "
+                    "hold rows of the keys; apply_gradients first" % (ev.name, len(ev.pending_grads)))
+        k = keys.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        n = C.c_int64(0)
+        check(lib().dr_ev_remove(p._h, ptr(k), k.numel(), C.byref(n), stream_handle(self.device)))
+        return n.value
+
+    def track_removals(self, on=True):
+        """Start (with an empty log) or stop logging the keys that shrink()
+        and remove() drop from the key space this EV shares with its slots;
+        save_incremental writes the log into the delta."""
+        self._require_int64_keys("track_removals")
+        check(lib().dr_ev_track_removals(self._h, 1 if on else 0, stream_handle(self.device)))
+
+    def tracking_removals(self):
+        return lib().dr_ev_tracking_removals(self._h) == 1
+
+    def removed_count(self):
+        """Entries in the removal log: an upper bound on len(export_removed())."""
+        n = C.c_int64(0)
+        check(lib().dr_ev_removed_count(self._h, C.byref(n), stream_handle(self.device)))
+        return n.value
+
+    def export_removed(self):
+        """The distinct logged keys, ascending (device int64).  The log is not
+        filtered against the map and stays in place (clear_removed)."""
+        self._require_int64_keys("export_removed")
+        st = stream_handle(self.device)
+        m = C.c_int64(0)
+        check(lib().dr_ev_removed_count(self._h, C.byref(m), st))
+        keys = torch.empty(m.value, dtype=torch.int64, device=self.device)
+        if m.value:
+            check(lib().dr_ev_export_removed(self._h, ptr(keys), m.value, C.byref(m), st))
+        return keys[:m.value]
+
+    def clear_removed(self):
+        check(lib().dr_ev_clear_removed(self._h, stream_handle(self.device)))
+
 
 def mark_updated_grouped(evs, keys, num_valid=None):
     """mark_updated over several EVs with one launch per device and

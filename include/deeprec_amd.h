@@ -648,6 +648,53 @@ int dr_ev_upsert(dr_ev* ev, const int64_t* keys, int64_t n, const void* values,
                  const int64_t* versions, const int64_t* freqs, int64_t partition_id,
                  int64_t partition_num, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Keyed removal and the removal log: how a delta carries evictions         */
+/* (build-defined).                                      */
+/* ------------------------------------------------------------------------ */
+/* Remove the given keys (device int64[n]) from the key space of a primary  */
+/* EV: dr_ev_shrink's semantics with the list as the selection rule.        */
+/* A key is removed if and only if it is in the map, published and live     */
+/* (row assigned and not dead).  Neither the first-touch bits nor the       */
+/* Counter rule is consulted: a key in the map below filter_freq goes too.  */
+/* Key -1 (the special slot) and key 0 are ordinary members of the list.    */
+/* Absent keys are ignored; duplicates count once.  *removed_host           */
+/* (nullable) = distinct keys removed, and dr_ev_size drops by that much.   */
+/* Rows stay allocated until dr_ev_compact, exactly as after dr_ev_shrink;  */
+/* the removed rows' update-tracking bits, freq and version are left alone  */
+/* (dr_ev_export_updated skips keys that are not in the map, and            */
+/* dr_ev_compact clears a hole's bit and resets the tail).  Bloom EVs are   */
+/* accepted; their counters are untouched, as under shrink.  The kept slots */
+/* are rehashed into a fresh table (linear probing has no tombstones), so   */
+/* A CALL COSTS ONE PASS OVER THE WHOLE SLOT TABLE WHATEVER n IS: batch the */
+/* keys.  n == 0 returns DR_OK and touches nothing.  The slot-table pointer */
+/* changes, as under shrink.  Synchronises; refused inside stream capture;  */
+/* a slot EV is DR_INVALID_ARGUMENT.                                        */
+int dr_ev_remove(dr_ev* ev, const int64_t* keys, int64_t n, int64_t* removed_host /* nullable */,
+                 void* stream);
+/* The removal log of a key space: while it is on, dr_ev_shrink and         */
+/* dr_ev_remove append every key they drop (a device int64 buffer that      */
+/* grows geometrically).  Independent of update tracking; Bloom EVs are     */
+/* accepted.  on != 0: start with an empty log (a log that is already on is */
+/* kept); on == 0: drop it.  With the log off dr_ev_shrink launches and     */
+/* reads exactly what it did without this feature.  May synchronise.        */
+int dr_ev_track_removals(dr_ev* ev, int on, void* stream);
+/* 1 when the EV's key space logs removals, 0 when not, -1 for a null EV.   */
+int dr_ev_tracking_removals(dr_ev* ev);
+/* Log entries: an UPPER BOUND on what dr_ev_export_removed returns (a key  */
+/* evicted, re-created and evicted again is logged twice).  Host value.     */
+int dr_ev_removed_count(dr_ev* ev, int64_t* n_host, void* stream);
+/* Distinct logged keys, ascending as signed int64 (radix sort, duplicates  */
+/* collapsed on the device).  The log is NOT filtered against the current   */
+/* map: a key that was evicted and is live again is still exported.         */
+/* keys_out NULL queries the count into *m_host; capacity < distinct count  */
+/* is DR_INVALID_ARGUMENT with *m_host set to the count needed.  The log    */
+/* stays (dr_ev_clear_removed).  Syncs.                                     */
+int dr_ev_export_removed(dr_ev* ev, int64_t* keys_out, int64_t capacity, int64_t* m_host,
+                         void* stream);
+/* Empty the log (the buffer is kept).  Host side only.                     */
+int dr_ev_clear_removed(dr_ev* ev, void* stream);
+
 /* Per-key freq / version of the primary, host-side, syncs (tests/debug).   */
 int dr_ev_key_meta(dr_ev* ev, const int64_t* keys_host, int64_t n, int64_t* freq_host,
                    int64_t* version_host, int32_t* has_row_host, void* stream);
