@@ -3677,6 +3677,7 @@ int dr_ev_apply_adam(dr_ev* var, dr_ev* m, dr_ev* v, float beta1_power, float be
 // with the row, so a bit stays with its key for the key's lifetime; the bit
 // of an evicted key stays set and selects nothing until a compaction clears it.
 //   mark   : lane per key, the read-only probe of the primary column, atomicOr
+//            (by row: lane per row a lookup resolved, no probe)
 //   export : scan the cap + 1 slots (16-B loads, wave ballots, one append per
 //            block tile), radix sort on the sign-flipped key, gather
 //   upsert : ev_import_kernel, then every accepted row is written
@@ -3715,6 +3716,49 @@ __global__ __launch_bounds__(256) void ev_mark_updated_kernel(MarkGroup g, int T
   uint32_t* w = bits + (row >> 5);
   const uint32_t m = 1u << (row & 31);
   if (!(gld(w) & m)) atomicOr(w, m);  // (a repeated key finds its bit set)
+}
+
+// The mark by ROW: the rows a lookup of these EVs resolved (the row-grouped
+// backward's rowsel), so no probe.  Position order (rec_t == 0: table t's rows
+// are rowsel[koff[t] .. koff[t + 1]), optional device counts) or the one-hot
+// training lookup's record-major [batch, T] block (rec_t == T: one contiguous
+// stream, position j belongs to table j % T).  8 B read per position.
+struct RowMarkGroup {
+  uint32_t* bits[DR_MAX_GROUP];  // nullptr: not tracking, or the table is left out
+  int64_t row_cap[DR_MAX_GROUP];
+  int64_t koff[DR_MAX_GROUP + 1];
+  const int64_t* n_dev[DR_MAX_GROUP];
+};
+static_assert(sizeof(RowMarkGroup) + 64 <= 4096, "row mark kernel arguments exceed 4 KiB");
+
+__global__ __launch_bounds__(256) void ev_mark_updated_rows_kernel(
+    RowMarkGroup g, int T, int rec_t, const int64_t* __restrict__ rowsel) {
+  __shared__ uint32_t* sb[DR_MAX_GROUP];
+  __shared__ int64_t sr[DR_MAX_GROUP];
+  if (threadIdx.x < T) {
+    sb[threadIdx.x] = g.bits[threadIdx.x];
+    sr[threadIdx.x] = g.row_cap[threadIdx.x];
+  }
+  __syncthreads();
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t i = first + threadIdx.x;
+  if (i >= g.koff[T]) return;
+  int t;
+  if (rec_t) {
+    // (the block's first position reduced once, uniformly; 32-bit per lane)
+    t = (int)(((unsigned)(first % rec_t) + threadIdx.x) % (unsigned)rec_t);
+  } else {
+    t = table_of(g.koff, T, i, first);
+    const int64_t li = i - g.koff[t];
+    if (li < 0 || (g.n_dev[t] && li >= *g.n_dev[t])) return;
+  }
+  uint32_t* bits = sb[t];
+  if (!bits) return;
+  const int64_t row = rowsel[i];
+  if (row < 0 || row >= sr[t]) return;  // a default served on an exhausted pool, or no row
+  uint32_t* w = bits + (row >> 5);
+  const uint32_t m = 1u << (row & 31);
+  if (!(gld(w) & m)) atomicOr(w, m);
 }
 
 __global__ __launch_bounds__(256) void ev_dirty_count_kernel(const uint32_t* __restrict__ bits,
@@ -3928,6 +3972,50 @@ int dr_ev_mark_updated(dr_ev* const* evs, int num_tables, const int64_t* keys,
   if (!any) return DR_OK;
   hipLaunchKernelGGL(ev_mark_updated_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0,
                      S(stream), g, T, keys);
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+int dr_ev_mark_updated_rows(dr_ev* const* evs, int num_tables, const int64_t* rowsel,
+                            const int64_t* koff_host, int rows_record,
+                            const int64_t* const* n_dev_per_table, void* stream) {
+  using namespace dr;
+  const int T = num_tables;
+  DR_REQUIRE(evs && koff_host && T >= 1 && T <= DR_MAX_GROUP, DR_INVALID_ARGUMENT, "bad argument");
+  bool some = false;
+  for (int t = 0; t < T; ++t) {
+    DR_REQUIRE(koff_host[t] >= 0 && koff_host[t + 1] >= koff_host[t], DR_INVALID_ARGUMENT,
+               "koff must be non-decreasing from >= 0");
+    some = some || evs[t];
+  }
+  DR_REQUIRE(some, DR_INVALID_ARGUMENT, "every ev is null");
+  const int64_t total = koff_host[T];
+  DR_REQUIRE(total == 0 || rowsel, DR_INVALID_ARGUMENT, "null rowsel");
+  if (rows_record) {
+    DR_REQUIRE(!n_dev_per_table, DR_INVALID_ARGUMENT,
+               "record-major rows take no per-table device counts");
+    for (int t = 0; t <= T; ++t)
+      DR_REQUIRE(koff_host[t] == t * koff_host[1], DR_INVALID_ARGUMENT,
+                 "record-major rows need koff[t] == t * batch (table %d)", t);
+  }
+  EvGuard guard_(evs, T);  // (null tables are left out)
+  if (total == 0) return DR_OK;
+  RowMarkGroup g;
+  memset(&g, 0, sizeof(g));
+  bool any = false;
+  for (int t = 0; t < T; ++t) {
+    g.koff[t] = koff_host[t];
+    if (!evs[t]) continue;  // bits stay null: the table's range is skipped
+    const EvShared* s = evs[t]->sh;
+    g.bits[t] = s->dirty;
+    g.row_cap[t] = s->row_cap;
+    g.n_dev[t] = n_dev_per_table ? n_dev_per_table[t] : nullptr;
+    any = any || s->dirty;
+  }
+  g.koff[T] = total;
+  if (!any) return DR_OK;
+  hipLaunchKernelGGL(ev_mark_updated_rows_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256),
+                     0, S(stream), g, T, rows_record ? T : 0, rowsel);
   DR_LAUNCH_CHECK();
   return DR_OK;
 }

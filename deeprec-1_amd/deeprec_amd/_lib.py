@@ -235,6 +235,7 @@ SIGNATURES = {
     "dr_ev_track_updates": (_I32, [_P, _I32, _P]),
     "dr_ev_tracking_updates": (_I32, [_P]),
     "dr_ev_mark_updated": (_I32, [_P, _I32, _P, _P, _P, _P]),
+    "dr_ev_mark_updated_rows": (_I32, [_P, _I32, _P, _P, _I32, _P, _P]),
     "dr_ev_updated_count": (_I32, [_P, _P, _P]),
     "dr_ev_export_updated": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P]),
     "dr_ev_clear_updated": (_I32, [_P, _P]),

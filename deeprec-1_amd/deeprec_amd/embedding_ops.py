@@ -647,6 +647,21 @@ class _RowsPending(object):
                               rows=urows[k[t]:k[t + 1]])
                 for t in range(T)]
 
+    def mark_rows(self, evs_to_mark, stream):
+        """Mark the forward's rows as updated in the key spaces of
+        `evs_to_mark` (EVs of this group that track updates): one
+        dr_ev_mark_updated_rows over the group's rowsel, a null table for
+        every other EV.  The gradient is not formed and no PendingRowSlices
+        attribute is read, so the group stays fusable."""
+        import ctypes as C
+        grp = self.group
+        T = len(grp.feats)
+        want = {id(e) for e in evs_to_mark}
+        handles = (C.c_void_p * T)(*[e.handle.value if id(e) in want else None
+                                     for e in self.evs])
+        check(lib().dr_ev_mark_updated_rows(handles, T, ptr(grp.rowsel), ops._koff_array(grp.koff),
+                                            int(grp.rows_record), None, stream))
+
     def apply_sgd(self, lr, global_step, stream):
         import ctypes as C
         grp = self.group

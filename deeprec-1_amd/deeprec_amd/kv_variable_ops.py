@@ -312,6 +312,7 @@ class EmbeddingVariable(object):
         self._slot_index = _slot_index
         self._lock = threading.Lock()
         self._tracking = False    # update tracking of the key space (held by the primary)
+        self._tracking_by_row = False   # ... marked by row in apply_gradients
         self.pending_grads = []
         opt = ev_option or EmbeddingVariableOption()
         f = opt.filter_option
@@ -552,25 +553,43 @@ class EmbeddingVariable(object):
                 _lib.INVALID_ARGUMENT, "%s needs an int64-key EmbeddingVariable (%s has %s keys)"
                 % (what, self.name, self.key_dtype))
 
-    def track_updates(self, on=True):
+    def track_updates(self, on=True, by_row=False):
         """Start (or stop) recording which keys of the key space this EV
         shares with its slots are updated: one bit per row, set by
         mark_updated -- the optimizers' apply_gradients marks the gradient's
-        indices, RecordSparseIndices' role -- and read by export_updated."""
+        indices, RecordSparseIndices' role -- and read by export_updated.
+        by_row: apply_gradients marks from the rows the forward resolved
+        (mark_updated_rows) wherever a pending gradient carries them -- no
+        probe of the key table, and a fused SGD group stays fused; the same
+        bits.  The flag holds until the next track_updates call."""
         self._require_int64_keys("track_updates")
         check(lib().dr_ev_track_updates(self._h, 1 if on else 0, stream_handle(self.device)))
-        (self._primary or self)._tracking = bool(on)
+        p = self._primary or self
+        p._tracking = bool(on)
+        p._tracking_by_row = bool(on) and bool(by_row)
 
     def tracking_updates(self):
         """Whether this EV's key space records updates (the host-side mirror
         of dr_ev_tracking_updates: no library call on the per-step path)."""
         return (self._primary or self)._tracking
 
+    def tracking_by_row(self):
+        """Whether the key space tracks updates and apply_gradients marks
+        them by row (track_updates(by_row=True))."""
+        return (self._primary or self)._tracking_by_row
+
     def mark_updated(self, keys, num_valid=None):
         """Mark `keys` (the first num_valid of them: device int64[1]) as
         updated.  Keys that are absent or whose primary row is untouched are
         ignored, nothing is created; a no-op while tracking is off."""
         mark_updated_grouped([self], [keys], [num_valid])
+
+    def mark_updated_rows(self, rows, num_valid=None):
+        """mark_updated by row: `rows` (the first num_valid of them) are rows
+        a lookup of this EV resolved (find(), a forward's recorded rows), with
+        no compact(), remove() or restore since.  Negative rows and rows past
+        the row capacity are ignored; a no-op while tracking is off."""
+        mark_updated_rows_grouped([self], [rows], [num_valid])
 
     def updated_count(self):
         """Number of marked rows: an upper bound on len(export_updated()[0])."""
@@ -723,17 +742,17 @@ class EmbeddingVariable(object):
         check(lib().dr_ev_clear_removed(self._h, stream_handle(self.device)))
 
 
-def mark_updated_grouped(evs, keys, num_valid=None):
-    """mark_updated over several EVs with one launch per device and
-    MAX_GROUP tables (dr_ev_mark_updated's grouping): keys[t], and the
-    optional device count num_valid[t], belong to evs[t].  EVs whose key
-    space is not tracking are left out."""
+def _mark_grouped(what, evs, xs, num_valid, launch):
+    """The grouping of the two marks: xs[t] (keys or rows), and the optional
+    device count num_valid[t], belong to evs[t]; launch(handles, T, flat, koff,
+    nd, stream) once per device and MAX_GROUP tables.  EVs whose key space is
+    not tracking, and empty inputs, are left out."""
     by_dev = {}
     for t, ev in enumerate(evs):
-        if ev.tracking_updates() and keys[t].numel():
-            ev._require_int64_keys("mark_updated")
+        if ev.tracking_updates() and xs[t].numel():
+            ev._require_int64_keys(what)
             by_dev.setdefault(str(ev.device), []).append(
-                (ev, keys[t], None if num_valid is None else num_valid[t]))
+                (ev, xs[t], None if num_valid is None else num_valid[t]))
     for items in by_dev.values():
         while items:
             chunk, items = items[:_lib.MAX_GROUP], items[_lib.MAX_GROUP:]
@@ -745,7 +764,24 @@ def mark_updated_grouped(evs, keys, num_valid=None):
                 koff[t + 1] = koff[t] + ks[t].numel()
             handles = (C.c_void_p * T)(*[ev._h.value for ev, _, _ in chunk])
             nd = (C.c_void_p * T)(*[None if n is None else n.data_ptr() for _, _, n in chunk])
-            check(lib().dr_ev_mark_updated(handles, T, ptr(flat), koff, nd, stream_handle(dev)))
+            check(launch(handles, T, ptr(flat), koff, nd, stream_handle(dev)))
+
+
+def mark_updated_grouped(evs, keys, num_valid=None):
+    """mark_updated over several EVs with one launch per device and
+    MAX_GROUP tables (dr_ev_mark_updated's grouping): keys[t], and the
+    optional device count num_valid[t], belong to evs[t].  EVs whose key
+    space is not tracking are left out."""
+    _mark_grouped("mark_updated", evs, keys, num_valid, lib().dr_ev_mark_updated)
+
+
+def mark_updated_rows_grouped(evs, rows, num_valid=None):
+    """mark_updated_rows over several EVs, grouped as mark_updated_grouped
+    (dr_ev_mark_updated_rows, position order): rows[t], and the optional
+    device count num_valid[t], belong to evs[t]."""
+    _mark_grouped("mark_updated_rows", evs, rows, num_valid,
+                  lambda h, T, flat, koff, nd, st:
+                  lib().dr_ev_mark_updated_rows(h, T, flat, koff, 0, nd, st))
 
 
 _EV_REGISTRY = {}

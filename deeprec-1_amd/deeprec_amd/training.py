@@ -15,7 +15,8 @@ from . import ops
 from ._lib import check, lib, ptr, stream_handle
 from .embedding_ops import DenseTable
 from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
-                              _flush_deferred_releases, mark_updated_grouped)
+                              _flush_deferred_releases, mark_updated_grouped,
+                              mark_updated_rows_grouped)
 
 
 def _concat(slices):
@@ -149,15 +150,47 @@ class _Optimizer(object):
         """RecordSparseIndices' role (incremental_saver.py): every EV whose key
         space tracks updates gets the indices of its pending slices marked
         (honouring num_valid) before they are consumed.  Reading the indices
-        forms a PendingRowSlices' gradient, so a fused row group with a
-        tracked EV takes the ordinary path -- the same values.  Nothing runs
-        for an EV that is not tracking."""
+        forms a PendingRowSlices' gradient, so a fused row group with an EV
+        tracked by key takes the ordinary path -- the same values.  An EV
+        tracked by row (track_updates(by_row=True)) is marked from the rows
+        the forward resolved instead: a still unformed PendingRowSlices from
+        its group's rowsel (one launch per group, the gradient stays unformed
+        and the group fused), a formed slice from its `rows`; a slice without
+        rows (the sharded engines') and a Counter-filter EV are marked by key.
+        Nothing runs for an EV that is not tracking."""
         marks = [(var, sl) for var in var_list
                  if isinstance(var, EmbeddingVariable) and var.tracking_updates()
                  for sl in var.pending_grads]
+        if not marks:
+            return
+        by_row = [(var, sl) for var, sl in marks
+                  if var.tracking_by_row() and var.filter_freq == 0]
+        if by_row:
+            marks = [(var, sl) for var, sl in marks
+                     if not (var.tracking_by_row() and var.filter_freq == 0)]
         if marks:   # one launch per device and MAX_GROUP slices
             mark_updated_grouped([var for var, _ in marks], [sl.indices for _, sl in marks],
                                  [sl.num_valid for _, sl in marks])
+        if not by_row:
+            return
+        # (after the marks by key: a group those formed is no longer fusable,
+        # and its by-row members have rows)
+        groups, formed, keyed = {}, [], []
+        for var, sl in by_row:
+            if isinstance(sl, PendingRowSlices) and sl.fusable():
+                groups.setdefault(id(sl._pending), (sl._pending, []))[1].append(var)
+            elif sl.rows is not None:
+                formed.append((var, sl))
+            else:
+                keyed.append((var, sl))
+        for pend, vs in groups.values():
+            pend.mark_rows(vs, stream_handle(pend.dev))
+        if formed:
+            mark_updated_rows_grouped([var for var, _ in formed], [sl.rows for _, sl in formed],
+                                      [sl.num_valid for _, sl in formed])
+        if keyed:
+            mark_updated_grouped([var for var, _ in keyed], [sl.indices for _, sl in keyed],
+                                 [sl.num_valid for _, sl in keyed])
 
     def _apply_fused_rows(self, var_list, gs):
         """SGD over every EV of a row-grouped lookup backward whose gradient

@@ -623,6 +623,33 @@ int dr_ev_tracking_updates(dr_ev* ev);
 int dr_ev_mark_updated(dr_ev* const* evs, int num_tables, const int64_t* keys,
                        const int64_t* koff_host, const int64_t* const* n_dev_per_table,
                        void* stream);
+/* The same mark by ROW: rowsel holds rows that a lookup of these EVs        */
+/* resolved, in the layouts of the row-grouped backward                      */
+/* (dr_pool_grad_rows_grouped_ex2, dr_ev_pool_grad_rows_apply_sgd_ex):       */
+/*   rows_record == 0  table t's rows are rowsel[koff[t] .. koff[t+1]);      */
+/*                     n_dev_per_table[t] (device int64[1], optional) limits */
+/*                     table t to its first *n positions;                    */
+/*   rows_record != 0  rowsel is the record-major [batch, T] block of a      */
+/*                     one-hot training lookup, position j belonging to      */
+/*                     table j % T; koff[t] == t * batch is required and     */
+/*                     n_dev_per_table refused.                              */
+/* Row r of table t is marked if and only if evs[t] is non-null, its key     */
+/* space is tracking and 0 <= r < row_capacity.  A negative row (a default   */
+/* served on an exhausted pool: it gets no gradient either) and a row out of */
+/* range are skipped; a NULL evs[t] skips table t's range (a group of which  */
+/* only some EVs are marked), but not every evs[t] may be NULL.  One kernel  */
+/* that reads 8 B per position: no probe, no keys, no workspace, no host     */
+/* read, no synchronisation, so it may sit in a captured step.  With a total */
+/* of 0, or no table tracking, DR_OK without a launch.                       */
+/* CONTRACT: the rows must come from a lookup of these EVs, and no           */
+/* dr_ev_compact, dr_ev_remove or restore of the key space may come between  */
+/* that lookup and the mark: those give a row to another key (or to none),   */
+/* and the mark would then name the wrong key.  Growth and dr_ev_shrink keep */
+/* a key's row.  The Python layer guarantees this for pending gradients      */
+/* (compact() and remove() refuse while a gradient is pending).              */
+int dr_ev_mark_updated_rows(dr_ev* const* evs, int num_tables, const int64_t* rowsel,
+                            const int64_t* koff_host, int rows_record,
+                            const int64_t* const* n_dev_per_table, void* stream);
 /* Number of marked rows: an UPPER BOUND on what dr_ev_export_updated       */
 /* returns (rows of evicted keys -- until dr_ev_compact clears their bits -- */
 /* and rows whose column is untouched still count).  Syncs.                 */

@@ -10,13 +10,21 @@ its two sides alternated three times (medians and run-to-run spreads):
           16 B x (cap + 1) is added.
   train   the bench's embedding train step (embedding_lookup_sparse_multi
           one-hot forward, backward, apply_gradients; eager) over T tables:
-          tracking off against on, for SGD and for Adagrad.  For SGD a third
-          arm runs with tracking off and the fused backward + update disabled
-          (the ordinary path a tracked group takes), so the loss of the fused
-          path and the mark itself show separately; the marks of one step
-          (grouped launches) are also timed alone with device events.
+          tracking off against on by key (track_updates()) and on by row
+          (track_updates(by_row=True)), for SGD and for Adagrad.  For SGD a
+          fourth arm runs with tracking off and the fused backward + update
+          disabled (the ordinary path a group tracked by key takes), so the
+          loss of the fused path and the mark itself show separately; the
+          marks of one step (grouped launches: by key, and by row over the
+          forward's record-major rows) are also timed alone with device
+          events.  With --kernel-stats (a rocprofv3 --kernel-trace --stats CSV
+          of a run of this part) the device time of the two mark kernels is
+          added.
 
-usage: python tools/incr_checkpoint_ab.py [--part export|train|all] [--rows 2000000]
+  mark-stats  only reads --kernel-stats and prints the mark kernels' device
+          time (the traced run is a run of its own, with few steps).
+
+usage: python tools/incr_checkpoint_ab.py [--part export|train|all|mark-stats] [--rows 2000000]
            [--dim 128] [--marked 65536] [--train-tables 26] [--train-rows 4000000]
            [--batch 65536] [--steps 20] [--kernel-stats CSV] [--out profiles/incr_checkpoint.json]"""
 import argparse
@@ -120,22 +128,23 @@ def part_train(args, dr, dev):
             out.backward(upstream)
             opt.apply_gradients(evs)
 
-    def track(on):
+    def track(on, by_row=False):
         for ev in evs:
-            ev.track_updates(on)
+            ev.track_updates(on, by_row=by_row)
 
     res = {"shape": {"tables": T, "rows": R, "dim": D, "batch": B, "steps": args.steps,
                      "graph": False}}
     for name, opt in (("sgd", dr.GradientDescentOptimizer(0.01)),
                       ("adagrad", dr.AdagradOptimizer(0.01))):
-        arms = [("off", False, True), ("on", True, True)]
+        arms = [("off", False, False, True), ("on", True, False, True),
+                ("on_row", True, True, True)]
         if name == "sgd":
-            arms.append(("off_unfused", False, False))
+            arms.append(("off_unfused", False, False, False))
         steps(opt, 4)                      # every batch once: slots exist, code loaded
         per = {a[0]: [] for a in arms}
         for _ in range(ROUNDS):
-            for arm, on, fused in arms:
-                track(on)
+            for arm, on, by_row, fused in arms:
+                track(on, by_row)
                 old, eo._FUSED_SGD = eo._FUSED_SGD, fused and eo._FUSED_SGD
                 try:
                     steps(opt, 2)
@@ -144,8 +153,15 @@ def part_train(args, dr, dev):
                     eo._FUSED_SGD = old
         track(False)
         res[name] = {arm + "_ms_per_step": _summary(v) for arm, v in per.items()}
-        res[name]["on_minus_off_ms"] = round(res[name]["on_ms_per_step"]["median"]
-                                             - res[name]["off_ms_per_step"]["median"], 4)
+        for arm in ("on", "on_row"):
+            res[name][arm + "_minus_off_ms"] = round(res[name][arm + "_ms_per_step"]["median"]
+                                                     - res[name]["off_ms_per_step"]["median"], 4)
+        # an improvement: by key's on - off exceeds by row's by more than the two spreads added
+        res[name]["row_saves_ms"] = round(res[name]["on_ms_per_step"]["median"]
+                                          - res[name]["on_row_ms_per_step"]["median"], 4)
+        res[name]["row_is_improvement"] = bool(
+            res[name]["row_saves_ms"] > res[name]["on_ms_per_step"]["spread"]
+            + res[name]["on_row_ms_per_step"]["spread"])
         if name == "sgd":
             res[name]["unfused_minus_fused_ms"] = round(
                 res[name]["off_unfused_ms_per_step"]["median"]
@@ -167,14 +183,51 @@ def part_train(args, dr, dev):
         torch.cuda.synchronize()
         if r:
             t_mark.append(a.elapsed_time(b))
-    track(False)
     res["mark_calls_per_step_ms"] = _summary(t_mark, 5)
+    # ... and by row, as apply_gradients issues it for a fused group: one launch
+    # over the forward's record-major rows, the gradient left unformed
+    track(True, by_row=True)
+    t_rows = []
+    for r in range(ROUNDS + 1):
+        out = dr.embedding_lookup_sparse_multi(evs, sps[r % len(sps)], combiner="sum")
+        out.backward(upstream)
+        pend = evs[0].pending_grads[-1]._pending
+        assert pend.group.rows_record and pend.fusable()
+        a.record()
+        pend.mark_rows(evs, dr._lib.stream_handle(dev))
+        b.record()
+        torch.cuda.synchronize()
+        assert pend.fusable()
+        if r:
+            t_rows.append(a.elapsed_time(b))
+        for ev in evs:
+            ev.pending_grads = []
+    track(False)
+    res["row_mark_call_per_step_ms"] = _summary(t_rows, 5)
+    res["row_mark_bytes"] = 8 * T * B
+    if args.kernel_stats:
+        res.update(mark_kernel_stats(args.kernel_stats))
+    return res
+
+
+def mark_kernel_stats(path):
+    """Device time of the two mark kernels from a rocprofv3 --kernel-trace
+    --stats CSV of a run of the train part."""
+    res = {}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            name = row.get("Name", "")
+            for kern in ("ev_mark_updated_rows_kernel", "ev_mark_updated_kernel"):
+                if kern + "(" in name or name.endswith(kern):
+                    us = lambda k: round(float(row[k]) / 1e3, 2) if row.get(k) else None
+                    res[kern] = {"avg_us": us("AverageNs"), "calls": int(row["Calls"]),
+                                 "min_us": us("MinNs"), "max_us": us("MaxNs")}
     return res
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=["export", "train", "all"])
+    ap.add_argument("--part", default="all", choices=["export", "train", "all", "mark-stats"])
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--marked", type=int, default=65536)
@@ -186,6 +239,9 @@ def main():
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.part == "mark-stats":      # the CSV alone: no device needed
+        print(json.dumps({"train": mark_kernel_stats(args.kernel_stats)}), flush=True)
+        return
     import deeprec_amd as dr
     dr.load()
     if not torch.cuda.is_available():
