@@ -4596,6 +4596,80 @@ static int log_dropped(EvShared* s, const uint8_t* keep, int64_t dropped, unsign
   return DR_OK;
 }
 
+// The removal both dr_ev_remove and dr_ev_shrink_to run once their own mark
+// step has chosen the victims.  begin() allocates and fills the three
+// temporaries: `keep` ((cap + 1) bytes, all 1, rounded up to whole words),
+// the counter `cnt` (0) and the fresh slot table.  The caller then enqueues a
+// mark step that clears the byte of every doomed slot and adds their number
+// to *cnt.  finish() rehashes the kept slots (ev_rehash_kept_kernel), reads
+// the count, appends the victims to the removal log while it is on, swaps the
+// table in and adds to `removed`.  `expect` >= 0 is the count the caller's
+// selection must have produced: another one is DR_INTERNAL and the table
+// stays.  finish() frees the temporaries on every path; after a failed
+// begin() nothing is held.  `mark_rc` is the caller's mark step's status.
+struct RemoveWs {
+  uint8_t* keep = nullptr;
+  unsigned long long* cnt = nullptr;
+  Slot* ns = nullptr;
+};
+
+static int remove_begin(EvShared* s, RemoveWs* w, hipStream_t st) {
+  const int64_t ns_ = s->cap + 1;
+  const size_t keep_bytes = (size_t)ceil_div(ns_, 4) * 4;  // whole words for the atomic AND
+  DR_HIP(hipMalloc(&w->keep, keep_bytes));
+  if (hipMalloc(&w->cnt, sizeof(unsigned long long)) != hipSuccess) {
+    (void)hipFree(w->keep);
+    DR_REQUIRE(false, DR_RESOURCE_EXHAUSTED, "remove: out of device memory");
+  }
+  if (hipMalloc(&w->ns, (size_t)ns_ * sizeof(Slot)) != hipSuccess) {
+    (void)hipFree(w->keep);
+    (void)hipFree(w->cnt);
+    DR_REQUIRE(false, DR_RESOURCE_EXHAUSTED, "remove: out of device memory");
+  }
+  int rc = fill_bytes(w->cnt, 0, sizeof(unsigned long long), st);
+  if (!rc) rc = fill_bytes(w->keep, 1, keep_bytes, st);
+  if (!rc) rc = fill_bytes(w->ns, 0xFF, (size_t)ns_ * sizeof(Slot), st);
+  if (rc) {
+    (void)hipFree(w->keep);
+    (void)hipFree(w->cnt);
+    (void)hipFree(w->ns);
+  }
+  return rc;
+}
+
+static int remove_finish(EvShared* s, RemoveWs* w, int mark_rc, int64_t expect, const char* what,
+                         int64_t* removed_host, hipStream_t st) {
+  const int64_t ns_ = s->cap + 1;
+  int rc = mark_rc;
+  unsigned long long removed = 0;
+  if (!rc) {
+    hipLaunchKernelGGL(ev_rehash_kept_kernel, dim3((unsigned)ceil_div(ns_, 256)), dim3(256), 0, st,
+                       s->slots, s->cap, w->keep, w->ns);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+        hipMemcpy(&removed, w->cnt, sizeof(removed), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = DR_INTERNAL;
+  }
+  const bool miscount = !rc && expect >= 0 && (int64_t)removed != expect;
+  if (miscount) rc = DR_INTERNAL;
+  if (s->rm_log && !rc) rc = log_dropped(s, w->keep, (int64_t)removed, w->cnt, st);
+  (void)hipFree(w->keep);
+  (void)hipFree(w->cnt);
+  if (rc) {
+    (void)hipFree(w->ns);
+    if (miscount)
+      set_error("%s: %lld keys selected of %lld to evict", what, (long long)removed,
+                (long long)expect);
+    else
+      set_error("%s failed", what);
+    return rc;
+  }
+  (void)hipFree(s->slots);
+  s->slots = w->ns;
+  s->removed += (int64_t)removed;
+  if (removed_host) *removed_host = (int64_t)removed;
+  return DR_OK;
+}
+
 }  // namespace dr
 
 extern "C" {
@@ -4614,48 +4688,13 @@ int dr_ev_remove(dr_ev* ev, const int64_t* keys, int64_t n, int64_t* removed_hos
              "dr_ev_remove synchronises: not inside stream capture");
   if (n == 0) return DR_OK;
   std::lock_guard<std::mutex> g(s->mu);
-  const int64_t ns_ = s->cap + 1;
-  const size_t keep_bytes = (size_t)ceil_div(ns_, 4) * 4;  // whole words for the atomic AND
-  uint8_t* keep = nullptr;
-  unsigned long long* cnt = nullptr;
-  Slot* ns = nullptr;
-  DR_HIP(hipMalloc(&keep, keep_bytes));
-  if (hipMalloc(&cnt, sizeof(unsigned long long)) != hipSuccess) {
-    (void)hipFree(keep);
-    DR_REQUIRE(false, DR_RESOURCE_EXHAUSTED, "remove: out of device memory");
-  }
-  if (hipMalloc(&ns, (size_t)ns_ * sizeof(Slot)) != hipSuccess) {
-    (void)hipFree(keep);
-    (void)hipFree(cnt);
-    DR_REQUIRE(false, DR_RESOURCE_EXHAUSTED, "remove: out of device memory");
-  }
-  int rc = fill_bytes(cnt, 0, sizeof(unsigned long long), st);
-  if (!rc) rc = fill_bytes(keep, 1, keep_bytes, st);
-  if (!rc) rc = fill_bytes(ns, 0xFF, (size_t)ns_ * sizeof(Slot), st);
-  unsigned long long removed = 0;
-  if (!rc) {
-    hipLaunchKernelGGL(ev_remove_mark_kernel,
-                       dim3((unsigned)ceil_div(n, 256 * kRmMarkItems)), dim3(256), 0, st,
-                       s->slots, s->cap, keys, n, reinterpret_cast<uint32_t*>(keep), cnt);
-    hipLaunchKernelGGL(ev_rehash_kept_kernel, dim3((unsigned)ceil_div(ns_, 256)), dim3(256), 0, st,
-                       s->slots, s->cap, keep, ns);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
-        hipMemcpy(&removed, cnt, sizeof(removed), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = DR_INTERNAL;
-  }
-  if (s->rm_log && !rc) rc = log_dropped(s, keep, (int64_t)removed, cnt, st);
-  (void)hipFree(keep);
-  (void)hipFree(cnt);
-  if (rc) {
-    (void)hipFree(ns);
-    set_error("dr_ev_remove failed");
-    return rc;
-  }
-  (void)hipFree(s->slots);
-  s->slots = ns;
-  s->removed += (int64_t)removed;
-  if (removed_host) *removed_host = (int64_t)removed;
-  return DR_OK;
+  RemoveWs w;
+  int rc = remove_begin(s, &w, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ev_remove_mark_kernel,
+                     dim3((unsigned)ceil_div(n, 256 * kRmMarkItems)), dim3(256), 0, st,
+                     s->slots, s->cap, keys, n, reinterpret_cast<uint32_t*>(w.keep), w.cnt);
+  return remove_finish(s, &w, DR_OK, -1, "dr_ev_remove", removed_host, st);
 }
 
 int dr_ev_track_removals(dr_ev* ev, int on, void* stream) {
@@ -4759,6 +4798,477 @@ int dr_ev_export_removed(dr_ev* ev, int64_t* keys_out, int64_t capacity, int64_t
   DR_LAUNCH_CHECK();
   DR_HIP(hipStreamSynchronize(st));  // the temporaries go with this call
   return DR_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Key budget (dr_ev_shrink_to): evict the coldest keys down to max_keys
+// (DESIGN section 15).  The victims are the E = N - max_keys smallest live
+// entries by the 128-bit composite (metric, key), both words biased by the
+// sign bit so that unsigned order is signed order; keys are distinct, so the
+// set is unique.  Nothing is sorted and nothing comes to the host but N:
+//   gather : one pass over the cap + 1 slots packs every live entry
+//            (slot_has_row) into dense arrays (metric, key, slot index); the
+//            metric is an 8-B load by row; places per block tile with one
+//            atomic add (ev_scan_updated_kernel's scheme); the counter ends as N.
+//            The same pass ANDs and ORs the words of a block's live entries
+//            into a partial per block, which the select's init folds: a digit
+//            in which AND and OR agree is the same in every entry, and its
+//            pass has nothing to count
+//   select : exact radix select of the E-th smallest composite, most
+//            significant 8-bit digit first, 16 passes of two launches:
+//              pass : a grid-stride loop over the candidates; those matching
+//                     the prefix chosen so far go into a 256-bin LDS histogram
+//                     of the pass's digit (a wave whose lanes agree adds once),
+//                     the block's non-zero bins into the global bins.  When the
+//                     previous pick found that the prefix keeps at most half of
+//                     the candidates, the pass also writes the matching ones
+//                     into a smaller buffer, and later passes read only those.
+//                     The pass of a digit that all live entries share returns
+//                     at once (versions are global steps: their upper bytes)
+//              pick : one block; takes the digit where the running count
+//                     crosses the remaining rank, extends the prefix, and
+//                     zeroes the bins.  The state lives in device memory: no
+//                     host synchronise between passes
+//   mark   : every gathered entry whose composite is <= the selected one
+//            clears keep[slot] (its own byte: a plain store) and is counted,
+//            one atomic per block tile.  From there the code is dr_ev_remove's.
+// ===========================================================================
+namespace dr {
+
+struct SelState {
+  uint64_t pre_m, pre_k;    // the digits chosen so far, in place
+  uint64_t mask_m, mask_k;  // the bits they cover
+  uint64_t same_m, same_k;  // the words of all live entries where they agree ...
+  uint64_t diff_m, diff_k;  // ... and the bits in which some differ
+  uint64_t rank;            // 1-based rank of the wanted entry among the matching candidates
+  uint64_t n;               // entries of the buffer the candidates are read from
+  uint64_t matched;         // candidates that match the prefix
+  unsigned long long out_n;  // entries the running pass wrote to the next buffer
+  uint32_t cur;             // buffer read: 0 = the gathered arrays, 1 / 2 = the two smaller ones
+  uint32_t compact;         // the next pass writes its matching candidates to the next buffer
+  uint32_t bad;             // a count did not add up (never; the host then fails the call)
+};
+
+// buffer 0: the gather's arrays (n entries, never written again); buffers 1 and 2
+// hold n / 2 + 1 and n / 4 + 1: a pass compacts only when at most half survive,
+// so 0 -> 1 -> 2 -> 1 -> ... always fits
+struct SelBufs {
+  uint64_t* m[3];
+  uint64_t* k[3];
+  int64_t room[3];
+};
+
+__device__ __forceinline__ uint32_t sel_next(uint32_t cur) { return cur == 1 ? 2u : 1u; }
+
+// digit d is the same in every live entry: its pass has nothing to count.  A
+// pass that has to compact runs all the same (the pick switches buffers after it).
+__device__ __forceinline__ bool sel_skip(int d, uint64_t diff_m, uint64_t diff_k, bool compact) {
+  return !compact && (((d < 8 ? diff_m : diff_k) >> (56 - 8 * (d & 7))) & 255ull) == 0ull;
+}
+
+// a gather block's partial: OR and AND of the metric and key words of its live entries
+// (a block without one writes the neutral values)
+enum { kAggOrM = 0, kAggOrK = 1, kAggAndM = 2, kAggAndK = 3, kAggWords = 4 };
+
+static constexpr int kSelItems = 8;
+
+__global__ __launch_bounds__(256) void ev_budget_gather_kernel(
+    const Slot* __restrict__ slots, int64_t cap, const int64_t* __restrict__ metric,
+    int64_t row_cap, int lru, uint64_t* __restrict__ mout, uint64_t* __restrict__ kout,
+    uint32_t* __restrict__ sout, int64_t bound, unsigned long long* __restrict__ count,
+    unsigned long long* __restrict__ agg) {
+  __shared__ unsigned wtot[4];
+  __shared__ unsigned long long sbase;
+  __shared__ unsigned long long wagg[4][4];
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t tile = (int64_t)blockIdx.x * (256 * kSelItems);
+  uint64_t key[kSelItems];
+  uint64_t met[kSelItems];
+  uint64_t mask[kSelItems];  // wave-uniform
+  unsigned mine = 0;
+  unsigned long long or_m = 0ull, or_k = 0ull, and_m = ~0ull, and_k = ~0ull;
+#pragma unroll
+  for (int j = 0; j < kSelItems; ++j) {
+    const int64_t i = tile + j * 256 + threadIdx.x;
+    bool hit = false;
+    key[j] = 0;
+    met[j] = 0;
+    if (i <= cap) {
+      const slot_v sv = gld(reinterpret_cast<const slot_v*>(slots + i));
+      if (slot_has_row(sv, i == cap)) {
+        const int64_t row = (int64_t)(sv.y & kRowMask);
+        if (row < row_cap) {  // (always for a published row: keeps the load in bounds)
+          hit = true;
+          int64_t v = gld(metric + row);
+          if (lru && v == -1) v = INT64_MAX;  // not yet stamped: newest
+          met[j] = (uint64_t)v ^ (1ull << 63);
+          key[j] = (i < cap ? sv.x : kEmptyKey) ^ (1ull << 63);  // the special slot holds key -1
+          or_m |= met[j];
+          and_m &= met[j];
+          or_k |= key[j];
+          and_k &= key[j];
+        }
+      }
+    }
+    mask[j] = __ballot(hit);
+    mine += (unsigned)__popcll(mask[j]);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    or_m |= __shfl_xor(or_m, o, 64);
+    or_k |= __shfl_xor(or_k, o, 64);
+    and_m &= __shfl_xor(and_m, o, 64);
+    and_k &= __shfl_xor(and_k, o, 64);
+  }
+  if (lane == 0) {
+    wtot[wave] = mine;
+    wagg[wave][kAggOrM] = or_m;
+    wagg[wave][kAggOrK] = or_k;
+    wagg[wave][kAggAndM] = and_m;
+    wagg[wave][kAggAndK] = and_k;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    sbase = t ? atomicAdd(count, (unsigned long long)t) : 0ull;
+  }
+  // the block's partial is stored, not added to one word: four more atomics per
+  // block on four addresses took the gather from 0.12 to 0.29 ms at 4 M keys
+  if (threadIdx.x < kAggWords) {
+    const int w = threadIdx.x;
+    const bool is_or = w == kAggOrM || w == kAggOrK;
+    unsigned long long v = wagg[0][w];
+    for (int i = 1; i < 4; ++i) v = is_or ? (v | wagg[i][w]) : (v & wagg[i][w]);
+    agg[(int64_t)blockIdx.x * kAggWords + w] = v;
+  }
+  __syncthreads();
+  int64_t pos = (int64_t)sbase;
+  for (int w = 0; w < wave; ++w) pos += wtot[w];
+#pragma unroll
+  for (int j = 0; j < kSelItems; ++j) {
+    if ((mask[j] >> lane) & 1ull) {
+      const int64_t p = pos + __popcll(mask[j] & lanemask_lt());
+      if (p < bound) {
+        mout[p] = met[j];
+        kout[p] = key[j];
+        sout[p] = (uint32_t)(tile + j * 256 + threadIdx.x);
+      }
+    }
+    pos += __popcll(mask[j]);
+  }
+}
+
+// One block: folds the gather blocks' partials and sets the select's state.
+__global__ __launch_bounds__(256) void ev_select_init_kernel(
+    SelState* __restrict__ st, unsigned long long* __restrict__ bins,
+    const unsigned long long* __restrict__ agg, int64_t agg_blocks, int64_t n, int64_t rank) {
+  __shared__ unsigned long long part[256][kAggWords];
+  bins[threadIdx.x] = 0ull;
+  unsigned long long a[kAggWords] = {0ull, 0ull, ~0ull, ~0ull};
+  for (int64_t i = threadIdx.x; i < agg_blocks; i += 256) {
+    a[kAggOrM] |= gld(agg + i * kAggWords + kAggOrM);
+    a[kAggOrK] |= gld(agg + i * kAggWords + kAggOrK);
+    a[kAggAndM] &= gld(agg + i * kAggWords + kAggAndM);
+    a[kAggAndK] &= gld(agg + i * kAggWords + kAggAndK);
+  }
+  for (int w = 0; w < kAggWords; ++w) part[threadIdx.x][w] = a[w];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 256; ++i) {
+      a[kAggOrM] |= part[i][kAggOrM];
+      a[kAggOrK] |= part[i][kAggOrK];
+      a[kAggAndM] &= part[i][kAggAndM];
+      a[kAggAndK] &= part[i][kAggAndK];
+    }
+    SelState s;
+    s.pre_m = s.pre_k = s.mask_m = s.mask_k = 0ull;
+    s.same_m = a[kAggAndM];
+    s.same_k = a[kAggAndK];
+    s.diff_m = a[kAggAndM] ^ a[kAggOrM];
+    s.diff_k = a[kAggAndK] ^ a[kAggOrK];
+    s.rank = (uint64_t)rank;
+    s.n = s.matched = (uint64_t)n;
+    s.out_n = 0ull;
+    s.cur = 0u;
+    s.compact = 0u;
+    s.bad = 0u;
+    *st = s;
+  }
+}
+
+// Pass d (0..15) of the select: digit d of the composite is byte 7 - (d & 7) of
+// the metric (d < 8) or of the key.  Every block reads the same state, so the
+// loop bounds and the branches on it are uniform across the block.
+__global__ __launch_bounds__(256) void ev_select_pass_kernel(SelBufs b, int d,
+                                                             SelState* __restrict__ st,
+                                                             unsigned long long* __restrict__ bins) {
+  __shared__ unsigned hist[256];
+  __shared__ unsigned wtot[4];
+  __shared__ unsigned long long sbase;
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const uint64_t pre_m = gld(&st->pre_m), pre_k = gld(&st->pre_k);
+  const uint64_t mask_m = gld(&st->mask_m), mask_k = gld(&st->mask_k);
+  const int64_t n = (int64_t)gld(&st->n);
+  const uint32_t cur = gld(&st->cur);
+  const bool compact = gld(&st->compact) != 0u;
+  if (cur > 2u || sel_skip(d, gld(&st->diff_m), gld(&st->diff_k), compact)) return;
+  const uint64_t* __restrict__ sm = b.m[cur];
+  const uint64_t* __restrict__ sk = b.k[cur];
+  const uint32_t nxt = sel_next(cur);
+  uint64_t* __restrict__ dm = b.m[nxt];
+  uint64_t* __restrict__ dk = b.k[nxt];
+  const int64_t room = b.room[nxt];
+  const bool from_key = d >= 8;
+  const int shift = 56 - 8 * (d & 7);
+  // the key word is needed to test a prefix that reaches into it, for its digit, or to copy it
+  const bool need_k = from_key || compact;
+  hist[threadIdx.x] = 0u;
+  __syncthreads();
+  for (int64_t tile = (int64_t)blockIdx.x * (256 * kSelItems); tile < n;
+       tile += (int64_t)gridDim.x * (256 * kSelItems)) {
+    uint64_t mm[kSelItems], kk[kSelItems];
+    uint64_t mask[kSelItems];  // wave-uniform
+    unsigned mine = 0;
+#pragma unroll
+    for (int j = 0; j < kSelItems; ++j) {
+      const int64_t i = tile + j * 256 + threadIdx.x;
+      bool match = false;
+      mm[j] = kk[j] = 0;
+      if (i < n) {
+        mm[j] = gld(sm + i);
+        if (need_k) kk[j] = gld(sk + i);
+        match = (mm[j] & mask_m) == pre_m && (kk[j] & mask_k) == pre_k;
+      }
+      const unsigned digit = (unsigned)(((from_key ? kk[j] : mm[j]) >> shift) & 255ull);
+      mask[j] = __ballot(match);
+      if (mask[j]) {
+        // versions are global steps: the lanes of a wave mostly agree, and 64
+        // adds on one LDS word would serialise -- one lane adds for all then
+        const unsigned first = (unsigned)__shfl((int)digit, __ffsll((long long)mask[j]) - 1, 64);
+        const bool same = __ballot(match && digit != first) == 0ull;
+        if (same) {
+          if (lane == 0) atomicAdd(&hist[first], (unsigned)__popcll(mask[j]));
+        } else if (match) {
+          atomicAdd(&hist[digit], 1u);
+        }
+      }
+      mine += (unsigned)__popcll(mask[j]);
+    }
+    if (compact) {
+      if (lane == 0) wtot[wave] = mine;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        sbase = t ? atomicAdd(&st->out_n, (unsigned long long)t) : 0ull;
+      }
+      __syncthreads();
+      int64_t pos = (int64_t)sbase;
+      for (int w = 0; w < wave; ++w) pos += wtot[w];
+#pragma unroll
+      for (int j = 0; j < kSelItems; ++j) {
+        if ((mask[j] >> lane) & 1ull) {
+          const int64_t p = pos + __popcll(mask[j] & lanemask_lt());
+          if (p < room) {
+            dm[p] = mm[j];
+            dk[p] = kk[j];
+          }
+        }
+        pos += __popcll(mask[j]);
+      }
+      __syncthreads();  // wtot / sbase are rewritten by the next tile
+    }
+  }
+  __syncthreads();
+  const unsigned h = hist[threadIdx.x];
+  if (h) atomicAdd(bins + threadIdx.x, (unsigned long long)h);
+}
+
+// After pass d: the candidates that matched the prefix are spread over the 256
+// bins.  Takes the digit at which the running count reaches the rank, keeps the
+// rank inside that bin, and decides whether the next pass compacts.
+__global__ __launch_bounds__(256) void ev_select_pick_kernel(SelBufs b, int d,
+                                                             SelState* __restrict__ st,
+                                                             unsigned long long* __restrict__ bins) {
+  __shared__ unsigned long long sb[256];
+  sb[threadIdx.x] = bins[threadIdx.x];
+  bins[threadIdx.x] = 0ull;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  SelState s = *st;
+  const int shift = 56 - 8 * (d & 7);
+  if (sel_skip(d, s.diff_m, s.diff_k, s.compact != 0u)) {
+    // the pass did not run: every candidate has the digit all live entries share
+    const uint64_t digit = ((d < 8 ? s.same_m : s.same_k) >> shift) & 255ull;
+    if (d < 8) {
+      s.pre_m |= digit << shift;
+      s.mask_m |= 255ull << shift;
+    } else {
+      s.pre_k |= digit << shift;
+      s.mask_k |= 255ull << shift;
+    }
+    *st = s;  // rank, matched and the buffer stay; compact stays 0
+    return;
+  }
+  unsigned long long total = 0;
+  for (int i = 0; i < 256; ++i) total += sb[i];
+  if (s.compact) {  // the pass wrote its matching candidates: they are the buffer now
+    s.cur = sel_next(s.cur);
+    if (s.out_n != total || (int64_t)s.out_n > b.room[s.cur]) s.bad = 1u;
+    s.n = s.bad ? 0ull : s.out_n;  // never read past what was written
+  }
+  s.out_n = 0ull;
+  if (s.rank < 1ull || s.rank > total) s.bad = 1u;
+  unsigned long long below = 0;
+  int digit = 255;
+  for (int i = 0; i < 256; ++i) {
+    if (below + sb[i] >= s.rank) {
+      digit = i;
+      break;
+    }
+    below += sb[i];
+  }
+  if (!s.bad) s.rank -= below;
+  s.matched = sb[digit];
+  if (d < 8) {
+    s.pre_m |= (uint64_t)digit << shift;
+    s.mask_m |= 255ull << shift;
+  } else {
+    s.pre_k |= (uint64_t)digit << shift;
+    s.mask_k |= 255ull << shift;
+  }
+  // worth a copy only when the new prefix drops at least half of what is read
+  // (and a later pass is left to read the copy)
+  s.compact = (d < 14 && 2ull * sb[digit] <= s.n) ? 1u : 0u;
+  *st = s;
+}
+
+// keep[slot] = 0 for every gathered entry at or below the selected composite.
+__global__ __launch_bounds__(256) void ev_budget_mark_kernel(
+    const uint64_t* __restrict__ m, const uint64_t* __restrict__ k,
+    const uint32_t* __restrict__ slot, int64_t n, int64_t cap, const SelState* __restrict__ st,
+    uint8_t* __restrict__ keep, unsigned long long* __restrict__ nremoved) {
+  __shared__ unsigned wtot[4];
+  const uint64_t tm = gld(&st->pre_m), tk = gld(&st->pre_k);
+  const bool bad = gld(&st->bad) != 0u;
+  const int64_t tile = (int64_t)blockIdx.x * (256 * kSelItems);
+  unsigned mine = 0;  // wave-uniform
+#pragma unroll
+  for (int j = 0; j < kSelItems; ++j) {
+    const int64_t i = tile + j * 256 + threadIdx.x;
+    bool doomed = false;
+    if (i < n && !bad) {
+      const uint64_t mi = gld(m + i), ki = gld(k + i);
+      doomed = mi < tm || (mi == tm && ki <= tk);
+      if (doomed) {
+        const int64_t sidx = (int64_t)gld(slot + i);
+        if (sidx <= cap) keep[sidx] = 0;
+      }
+    }
+    mine += (unsigned)__popcll(__ballot(doomed));
+  }
+  if (lane_id() == 0) wtot[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    if (t) atomicAdd(nremoved, (unsigned long long)t);
+  }
+}
+
+}  // namespace dr
+
+extern "C" {
+
+int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* removed_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && ev->col == 0, DR_INVALID_ARGUMENT, "shrink_to needs a primary EV");
+  DR_REQUIRE(max_keys >= 0, DR_INVALID_ARGUMENT, "shrink_to: max_keys %lld < 0",
+             (long long)max_keys);
+  DR_REQUIRE(policy == DR_EVICT_LRU || policy == DR_EVICT_LFU, DR_INVALID_ARGUMENT,
+             "shrink_to: unknown policy %d", policy);
+  EvShared* s = ev->sh;
+  DR_REQUIRE(policy != DR_EVICT_LRU || s->version, DR_INVALID_ARGUMENT,
+             "shrink_to: LRU needs the version column (steps_to_live != 0)");
+  DR_REQUIRE(policy != DR_EVICT_LFU || (s->freq && !s->bloom), DR_INVALID_ARGUMENT,
+             "shrink_to: LFU needs the freq column a Counter filter maintains");
+  hipStream_t st = S(stream);
+  if (removed_host) *removed_host = 0;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cs);
+  DR_REQUIRE(cs == hipStreamCaptureStatusNone, DR_INVALID_ARGUMENT,
+             "dr_ev_shrink_to synchronises: not inside stream capture");
+  std::lock_guard<std::mutex> g(s->mu);
+  DR_REQUIRE(s->cap < ((int64_t)1 << 32), DR_INVALID_ARGUMENT,
+             "shrink_to: %lld slots, the selection indexes < 2^32", (long long)s->cap);
+  // a live entry owns a row below top: top bounds the gather's arrays
+  int64_t top = 0;
+  DR_HIP(hipStreamSynchronize(st));
+  DR_HIP(hipMemcpy(&top, s->top, sizeof(int64_t), hipMemcpyDeviceToHost));
+  const int64_t bound = std::min<int64_t>(s->cap + 1, std::min<int64_t>(top, s->row_cap));
+  if (bound <= max_keys) return DR_OK;  // N <= bound: within the budget
+  const int64_t room1 = bound / 2 + 1, room2 = bound / 4 + 1;
+  const int64_t gather_blocks = ceil_div(s->cap + 1, 256 * kSelItems);
+  Carver sz(nullptr);
+  sz.take<uint64_t>(bound);
+  sz.take<uint64_t>(bound);
+  sz.take<uint32_t>(bound);
+  sz.take<uint64_t>(room1);
+  sz.take<uint64_t>(room1);
+  sz.take<uint64_t>(room2);
+  sz.take<uint64_t>(room2);
+  sz.take<unsigned long long>(256);
+  sz.take<SelState>(1);
+  sz.take<unsigned long long>(1);
+  sz.take<unsigned long long>(gather_blocks * kAggWords);
+  DevBuf buf;  // freed on every path
+  DR_HIP(buf.alloc(sz.used + 256, st));
+  Carver c(buf.p);
+  SelBufs b;
+  b.m[0] = c.take<uint64_t>(bound);
+  b.k[0] = c.take<uint64_t>(bound);
+  uint32_t* slot = c.take<uint32_t>(bound);
+  b.m[1] = c.take<uint64_t>(room1);
+  b.k[1] = c.take<uint64_t>(room1);
+  b.m[2] = c.take<uint64_t>(room2);
+  b.k[2] = c.take<uint64_t>(room2);
+  b.room[0] = bound;
+  b.room[1] = room1;
+  b.room[2] = room2;
+  unsigned long long* bins = c.take<unsigned long long>(256);
+  SelState* state = c.take<SelState>(1);
+  unsigned long long* count = c.take<unsigned long long>(1);
+  unsigned long long* agg = c.take<unsigned long long>(gather_blocks * kAggWords);
+  int rc = fill_bytes(count, 0, sizeof(unsigned long long), st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ev_budget_gather_kernel, dim3((unsigned)gather_blocks), dim3(256), 0, st,
+                     s->slots, s->cap, policy == DR_EVICT_LRU ? s->version : s->freq, s->row_cap,
+                     policy == DR_EVICT_LRU ? 1 : 0, b.m[0], b.k[0], slot, bound, count, agg);
+  DR_LAUNCH_CHECK();
+  unsigned long long live = 0;
+  DR_HIP(hipMemcpyAsync(&live, count, sizeof(live), hipMemcpyDeviceToHost, st));
+  DR_HIP(hipStreamSynchronize(st));
+  const int64_t N = (int64_t)live;
+  DR_REQUIRE(N <= bound, DR_INTERNAL, "shrink_to: %lld live entries over %lld rows", (long long)N,
+             (long long)bound);
+  if (N <= max_keys) return DR_OK;
+  const int64_t E = N - max_keys;
+  RemoveWs w;
+  rc = remove_begin(s, &w, st);
+  if (rc) return rc;
+  const unsigned tiles = (unsigned)ceil_div(N, 256 * kSelItems);
+  const unsigned pass_blocks = std::min<unsigned>(tiles, 2048u);
+  hipLaunchKernelGGL(ev_select_init_kernel, dim3(1), dim3(256), 0, st, state, bins, agg,
+                     gather_blocks, N, E);
+  for (int d = 0; d < 16; ++d) {
+    hipLaunchKernelGGL(ev_select_pass_kernel, dim3(pass_blocks), dim3(256), 0, st, b, d, state,
+                       bins);
+    hipLaunchKernelGGL(ev_select_pick_kernel, dim3(1), dim3(256), 0, st, b, d, state, bins);
+  }
+  hipLaunchKernelGGL(ev_budget_mark_kernel, dim3(tiles), dim3(256), 0, st, b.m[0], b.k[0], slot, N,
+                     s->cap, state, w.keep, w.cnt);
+  return remove_finish(s, &w, hipGetLastError() == hipSuccess ? DR_OK : DR_INTERNAL, E,
+                       "dr_ev_shrink_to", removed_host, st);
 }
 
 }  // extern "C"

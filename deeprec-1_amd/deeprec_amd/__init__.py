@@ -14,7 +14,7 @@ from .embedding_ops import (DenseTable, SparseTensor, embedding_lookup, embeddin
                             embedding_lookup_sparse_multi, fused_embedding_lookup_sparse,
                             safe_embedding_lookup_sparse)
 from .kv_variable_ops import (CBFFilter, CounterFilter, EmbeddingVariable, EmbeddingVariableOption,
-                              GlobalStepEvict, IndexedSlices, flush_releases,
+                              GlobalStepEvict, IndexedSlices, KeyBudgetEvict, flush_releases,
                               get_embedding_variable, read_only_lookups)
 from .ops import set_validate, status_check
 from .string_ops import StringTensor, string_to_hash_bucket_fast
@@ -26,7 +26,7 @@ __all__ = [
     "embedding_lookup", "embedding_lookup_sparse", "embedding_lookup_sparse_multi",
     "fused_embedding_lookup_sparse", "safe_embedding_lookup_sparse", "CBFFilter",
     "CounterFilter", "EmbeddingVariable", "EmbeddingVariableOption", "GlobalStepEvict",
-    "IndexedSlices", "get_embedding_variable", "read_only_lookups", "set_validate", "status_check",
+    "IndexedSlices", "KeyBudgetEvict", "get_embedding_variable", "read_only_lookups", "set_validate", "status_check",
     "AdagradOptimizer", "AdagradDecayOptimizer", "AdamAsyncOptimizer", "AdamOptimizer",
     "FtrlOptimizer", "GradientDescentOptimizer", "StringTensor",
     "string_to_hash_bucket_fast",

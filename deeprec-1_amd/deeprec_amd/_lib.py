@@ -246,6 +246,7 @@ SIGNATURES = {
     "dr_ev_removed_count": (_I32, [_P, _P, _P]),
     "dr_ev_export_removed": (_I32, [_P, _P, _I64, _P, _P]),
     "dr_ev_clear_removed": (_I32, [_P, _P]),
+    "dr_ev_shrink_to": (_I32, [_P, _I64, _I32, _P, _P]),
     "dr_ev_key_meta": (_I32, [_P, _P, _I64, _P, _P, _P, _P]),
     "dr_ev_apply_sgd": (_I32, [_P, _F32, _P, _P, _I64, _P, _I64, _P]),
     "dr_ev_apply_adagrad": (_I32, [_P, _P, _F32, _P, _P, _I64, _P, _I64, _P]),

@@ -475,17 +475,24 @@ def save(prefix, variables, global_step=None, compact=False):
     is shrunk first (EmbeddingVar::Shrink: by L2 weight when the EV has an
     l2_weight_threshold, else by global step when steps_to_live > 0), so
     evicted keys are not written; global_step None skips the step eviction.
+    A key space whose primary has a key budget (KeyBudgetEvict, max_keys > 0)
+    is then cut down to it (EmbeddingVariable.shrink_to), once, whether or not
+    global_step is given.
 
     compact=True also gives the evicted keys' rows back (EmbeddingVariable.
     compact): each distinct key space once, after its shrink and before its
     first dump.  The bundle's bytes do not depend on it."""
     w = BundleWriter(prefix)
     compacted = set()
+    budgeted = set()
     for name in variables:
         ev = variables[name]
         p = ev._primary or ev
         if p.l2_weight_threshold != -1.0 or (global_step is not None and p.steps_to_live > 0):
             ev.shrink(0 if global_step is None else global_step)
+        if p.max_keys > 0 and id(p) not in budgeted:
+            budgeted.add(id(p))
+            p.shrink_to(p.max_keys, p.policy)
         if compact and id(p) not in compacted:
             compacted.add(id(p))
             p.compact()
@@ -587,11 +594,15 @@ def save_incremental(prefix, variables, global_step=None):
     Evictions: with `global_step` given, a key space whose primary has
     steps_to_live > 0 or an l2_weight_threshold is shrunk first, exactly as
     save() does (global_step None shrinks nothing: eviction then stays with
-    the full save).  A key space that logs removals (track_removals()) also
+    the full save).  A key budget is different: a key space whose primary
+    has one (KeyBudgetEvict, max_keys > 0) is cut down to it
+    (EmbeddingVariable.shrink_to) whether or not global_step is given, after
+    that shrink -- the budget bounds the table, and a trainer that only writes
+    deltas must stay inside it too.  A key space that logs removals (track_removals()) also
     gets, under its PRIMARY's tensor key and after that name's five tensors,
     NAME-sparse_incr_removed_partition_offset (int32 [1001]) and
-    NAME-sparse_incr_removed_keys: the distinct keys shrink() / remove()
-    dropped since the log was last cleared, negative keys dropped and the
+    NAME-sparse_incr_removed_keys: the distinct keys shrink() / remove() /
+    shrink_to() dropped since the log was last cleared, negative keys dropped and the
     rest grouped by key % 1000; the log is cleared with the marks.  The
     primary of such a key space must be among `variables`.  A key space that
     does not log removals gets neither tensor and its delta carries no
@@ -610,6 +621,8 @@ def save_incremental(prefix, variables, global_step=None):
                 "under the primary's tensor key: name it in `variables`" % p.name)
         if global_step is not None and (p.l2_weight_threshold != -1.0 or p.steps_to_live > 0):
             p.shrink(global_step)
+        if p.max_keys > 0:
+            p.shrink_to(p.max_keys, p.policy)
     for name in variables:
         ev = variables[name]
         keys, vals, vers, frqs = ev.export_updated()

@@ -43,6 +43,24 @@ class GlobalStepEvict(object):
         self.steps_to_live = steps_to_live
 
 
+_EVICT_POLICIES = {"lru": 0, "lfu": 1}      # DR_EVICT_LRU / DR_EVICT_LFU
+
+
+class KeyBudgetEvict(object):
+    """A key budget for the table in HBM (build-defined):
+    at a save the key space keeps at most `max_keys` keys and the coldest go,
+    by version ("lru", needs steps_to_live != 0) or by freq ("lfu", needs a
+    CounterFilter).  max_keys 0 is off.  `steps_to_live` is GlobalStepEvict's,
+    so the age rule and the budget can be set together."""
+
+    def __init__(self, max_keys, policy="lru", steps_to_live=None):
+        if policy not in _EVICT_POLICIES:
+            raise ValueError("KeyBudgetEvict: policy is 'lru' or 'lfu', not %r" % (policy,))
+        self.max_keys = int(max_keys)
+        self.policy = policy
+        self.steps_to_live = steps_to_live
+
+
 class EmbeddingVariableOption(object):
     def __init__(self, ht_type="", ht_partition_num=1000, evict_option=None, filter_option=None):
         self.ht_type = ht_type
@@ -320,6 +338,9 @@ class EmbeddingVariable(object):
         if opt.evict_option is not None and opt.evict_option.steps_to_live:
             steps_to_live = opt.evict_option.steps_to_live
         self.steps_to_live = int(steps_to_live or 0)
+        # key budget applied by checkpoint.save / save_incremental (KeyBudgetEvict); 0 = off
+        self.max_keys = int(getattr(opt.evict_option, "max_keys", 0) or 0)
+        self.policy = getattr(opt.evict_option, "policy", "lru")
         # EmbeddingConfig::l2_weight_threshold (embedding_config.h:17,28): -1 = off
         self.l2_weight_threshold = float(l2_weight_threshold)
         _flush_deferred_releases()
@@ -708,6 +729,32 @@ class EmbeddingVariable(object):
         k = keys.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
         n = C.c_int64(0)
         check(lib().dr_ev_remove(p._h, ptr(k), k.numel(), C.byref(n), stream_handle(self.device)))
+        return n.value
+
+    def shrink_to(self, max_keys, policy="lru"):
+        """Key budget (dr_ev_shrink_to, through the primary as shrink()): when
+        the key space this EV shares with its slots holds more than `max_keys`
+        keys, the coldest go -- the first total_count() - max_keys by (version,
+        key) for "lru" (version -1, not yet stamped, counts as newest) or by
+        (freq, key) for "lfu" -- exactly as remove() of those keys: rows stay
+        allocated until compact() and the removal log gets them.  At or under
+        the budget nothing changes.  Returns the keys removed.  A queued
+        gradient (pending_grads of the primary or a slot EV) is refused, as in
+        remove(): its recorded rows would refer to dead keys."""
+        self._require_int64_keys("shrink_to")
+        if policy not in _EVICT_POLICIES:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "shrink_to: policy is 'lru' or 'lfu', not %r" % (policy,))
+        p = self._primary or self
+        for ev in [p] + list(p._slots.values()):
+            if ev.pending_grads:
+                raise _lib.InvalidArgumentError(
+                    _lib.INVALID_ARGUMENT, "shrink_to: %s has %d pending gradient(s), which may "
+                    "hold rows of the keys; apply_gradients first"
+                    % (ev.name, len(ev.pending_grads)))
+        n = C.c_int64(0)
+        check(lib().dr_ev_shrink_to(p._h, int(max_keys), _EVICT_POLICIES[policy], C.byref(n),
+                                    stream_handle(self.device)))
         return n.value
 
     def track_removals(self, on=True):

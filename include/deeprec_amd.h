@@ -722,6 +722,48 @@ int dr_ev_export_removed(dr_ev* ev, int64_t* keys_out, int64_t capacity, int64_t
 /* Empty the log (the buffer is kept).  Host side only.                     */
 int dr_ev_clear_removed(dr_ev* ev, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Key budget: evict the coldest keys down to max_keys (build-defined,      */
+/* DESIGN section 15; the rule of DeepRec's HBM-tier cache strategy with    */
+/* storage_size, without the lower tiers).                                  */
+/* ------------------------------------------------------------------------ */
+#define DR_EVICT_LRU 0   /* metric = version[row] */
+#define DR_EVICT_LFU 1   /* metric = freq[row]    */
+/* Live entries are the slots that reference a row (occupied, published,    */
+/* row not dead -- dr_ev_export's rule without the first-touch bits); the   */
+/* key -1 slot counts.  Their number N is what dr_ev_size returns.  Slots   */
+/* that are occupied without a published row, or with a dead row, are kept  */
+/* and do not count.                                                        */
+/* N <= max_keys: nothing changes at all -- no table swap, *removed_host =  */
+/* 0, the removal log as it was.                                            */
+/* N > max_keys: with E = N - max_keys, the live entries are ordered by     */
+/* (metric ascending as signed int64, then key ascending as signed int64 -- */
+/* dr_ev_export's key order) and the first E are evicted.  Keys are         */
+/* distinct, so the victim set is unique, and the call produces exactly     */
+/* that set (an exact radix select on the device; nothing but N comes to    */
+/* the host).                                                               */
+/* DR_EVICT_LRU: metric = version[row]; version -1 ("not yet stamped", as   */
+/* dr_ev_shrink reads it) ranks as INT64_MAX, i.e. newest, and is not       */
+/* rewritten; other negative versions rank as their signed value.           */
+/* DR_EVICT_LFU: metric = freq[row]; a key in the map below filter_freq is  */
+/* live and, having the smallest freq, goes first.                          */
+/* In every observable the call then equals dr_ev_remove(ev, <the E victim  */
+/* keys>), whose code it shares: kept slots are rehashed into a fresh       */
+/* table, dr_ev_size drops by E, the victims go to the removal log while it */
+/* is on, rows stay allocated until dr_ev_compact, *removed_host (nullable) */
+/* = E.  The selection does not read values: float, double and bf16 EVs and */
+/* EVs with slot columns all work.  Device temporaries: 32 B per live key,  */
+/* freed on every path.                                                     */
+/* DR_INVALID_ARGUMENT: a null EV (refused before any device is touched,    */
+/* *removed_host untouched) or a slot EV; max_keys < 0; an unknown policy;  */
+/* LRU on an EV without a version column (steps_to_live == 0); LFU on an EV */
+/* without a maintained freq column (no Counter filter, or a Bloom filter,  */
+/* whose freq is not maintained); inside stream capture (the call           */
+/* synchronises).  A selected count other than E is DR_INTERNAL and leaves  */
+/* the table as it was.                                                     */
+int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy,
+                    int64_t* removed_host /* nullable */, void* stream);
+
 /* Per-key freq / version of the primary, host-side, syncs (tests/debug).   */
 int dr_ev_key_meta(dr_ev* ev, const int64_t* keys_host, int64_t n, int64_t* freq_host,
                    int64_t* version_host, int32_t* has_row_host, void* stream);
