@@ -31,6 +31,8 @@ The device side is the engine's: `EmbeddingVariable.export()` (dr_ev_export,
 GPU), the 1000-way stable split (dr_partition_by_owner with world = 1000 +
 dr_rows_pack, GPU) and `import_partitioned()` (dr_ev_insert, GPU).  Only the
 file bytes pass through the host; checksums run natively (dr_crc32c_extend).
+Values keep the EV's dtype on disk: DT_FLOAT, DT_DOUBLE, or DT_BFLOAT16 for a
+bf16 EV (build-defined, like the bf16 EV itself).
 """
 import os
 import struct
@@ -50,6 +52,11 @@ _DT = {np.dtype(np.float32): 1, np.dtype(np.float64): 2, np.dtype(np.int32): 3,
        np.dtype(np.int64): 9, np.dtype(np.bool_): 10, np.dtype(np.uint16): 17,
        np.dtype(np.float16): 19, np.dtype(np.uint32): 22, np.dtype(np.uint64): 23}
 _NP = {v: k for k, v in _DT.items()}
+# DT_BFLOAT16 (types.proto): numpy has no bfloat16, so the rows of a bf16 EV
+# pass through the host as their raw 16-bit patterns -- written from a torch
+# bfloat16 tensor, read back as uint16 and viewed as bfloat16 by the import
+_DT_BFLOAT16 = 14
+_NP[_DT_BFLOAT16] = np.dtype(np.uint16)
 
 
 def crc32c(data, init=0):
@@ -332,15 +339,21 @@ class BundleWriter(object):
         if key in self._entries:
             raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
                                             "Adding duplicate key: %s" % key.decode())
+        code = None
         if torch.is_tensor(array):
+            if array.dtype == torch.bfloat16:
+                code = _DT_BFLOAT16
+                array = array.detach().contiguous().view(torch.int16)
             array = array.detach().cpu().numpy()
+            if code:
+                array = array.view(np.uint16)
         a = np.ascontiguousarray(array)
         if a.dtype not in _DT:
             raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, "unsupported dtype %s" % a.dtype)
         a = a.astype(a.dtype.newbyteorder("<"), copy=False)
         crc = crc32c(a) if a.nbytes else 0
         self._data.write(memoryview(a).cast("B") if a.nbytes else b"")
-        self._entries[key] = _entry_proto(_DT[a.dtype], a.shape, self._size, a.nbytes,
+        self._entries[key] = _entry_proto(code or _DT[a.dtype], a.shape, self._size, a.nbytes,
                                           mask_crc(crc))
         self._size += a.nbytes
 
@@ -424,8 +437,14 @@ def partition_snapshot(keys, values, versions, freqs):
     if n == 0:
         return offs, keys, values, versions, freqs
     ks, perm, counts = ops.partition_by_owner(keys.contiguous(), SAVED_PARTITION_NUM)
-    vals = torch.empty_like(values)
-    ops.rows_pack(values.contiguous(), perm, vals)
+    # rows move as their 32-bit words (dr_rows_pack counts a row in floats):
+    # a double row is 2 * dim of them, a bf16 row dim / 2
+    words = values.contiguous()
+    if words.dtype != torch.float32:
+        words = words.view(torch.float32)
+    vals = torch.empty_like(words)
+    ops.rows_pack(words, perm, vals)
+    vals = vals.view(values.dtype)
     p64 = perm.to(torch.int64)
     versions = versions[p64] if versions.numel() else versions
     freqs = freqs[p64] if freqs.numel() else freqs
@@ -526,10 +545,14 @@ def _import(ev, reader, tname, begin, end, filtered, partition_id, partition_num
         frqs = np.full(n, ev.filter_freq, np.int64)          # MinFreq
     dev = ev.device
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    if reader.entries[tname + "values"]["dtype"] == _DT_BFLOAT16:
+        vals = t(vals.view(np.int16)).view(torch.bfloat16)      # the raw bf16 patterns
+    else:
+        vals = t(vals)
     if not filtered:
         partition_id = partition_num = 0
     put = ev._upsert if upsert else ev.import_partitioned
-    put(t(keys), t(vals), t(vers), t(frqs), partition_id, partition_num)
+    put(t(keys), vals, t(vers), t(frqs), partition_id, partition_num)
 
 
 def restore_embedding_variable(ev, reader, name, partition_id=0, partition_num=1, suffix="",

@@ -120,7 +120,7 @@ class _Optimizer(object):
 
     def apply_gradients(self, var_list, global_step=None):
         gs = -1 if global_step is None else int(global_step)
-        self._record_updates(var_list)
+        late = self._record_updates(var_list)
         if self._opt == 0 and _KNOWN_ROWS:
             self._apply_fused_rows(var_list, gs)
         rounds = []   # rounds[r] = [(var, slices)] applied in one grouped launch
@@ -142,6 +142,8 @@ class _Optimizer(object):
                 raise TypeError("unsupported variable %r" % (var,))
         for items in rounds:
             self._apply_ev_batch(items, gs)
+        if late:
+            mark_updated_grouped(*late)
         self._finish()
         _flush_deferred_releases()   # EVs collected meanwhile (no-op while capturing)
 
@@ -157,22 +159,32 @@ class _Optimizer(object):
         its group's rowsel (one launch per group, the gradient stays unformed
         and the group fused), a formed slice from its `rows`; a slice without
         rows (the sharded engines') and a Counter-filter EV are marked by key.
-        Nothing runs for an EV that is not tracking."""
+        Nothing runs for an EV that is not tracking.
+
+        Returns the marks that have to wait for the applies, as
+        mark_updated_grouped's arguments, or None: the mark skips a key whose
+        primary row is untouched, and in a Counter-filter EV the apply itself
+        admits a key whose freq has reached filter_freq -- marked before it,
+        the key's first update would be missing from the next delta."""
         marks = [(var, sl) for var in var_list
                  if isinstance(var, EmbeddingVariable) and var.tracking_updates()
                  for sl in var.pending_grads]
         if not marks:
-            return
-        by_row = [(var, sl) for var, sl in marks
-                  if var.tracking_by_row() and var.filter_freq == 0]
+            return None
+        late = [(var, sl) for var, sl in marks if var.filter_freq > 0]
+        if late:
+            marks = [(var, sl) for var, sl in marks if var.filter_freq == 0]
+            # (the indices are read here, before the slices are consumed)
+            late = ([var for var, _ in late], [sl.indices for _, sl in late],
+                    [sl.num_valid for _, sl in late])
+        by_row = [(var, sl) for var, sl in marks if var.tracking_by_row()]
         if by_row:
-            marks = [(var, sl) for var, sl in marks
-                     if not (var.tracking_by_row() and var.filter_freq == 0)]
+            marks = [(var, sl) for var, sl in marks if not var.tracking_by_row()]
         if marks:   # one launch per device and MAX_GROUP slices
             mark_updated_grouped([var for var, _ in marks], [sl.indices for _, sl in marks],
                                  [sl.num_valid for _, sl in marks])
         if not by_row:
-            return
+            return late or None
         # (after the marks by key: a group those formed is no longer fusable,
         # and its by-row members have rows)
         groups, formed, keyed = {}, [], []
@@ -191,6 +203,7 @@ class _Optimizer(object):
         if keyed:
             mark_updated_grouped([var for var, _ in keyed], [sl.indices for _, sl in keyed],
                                  [sl.num_valid for _, sl in keyed])
+        return late or None
 
     def _apply_fused_rows(self, var_list, gs):
         """SGD over every EV of a row-grouped lookup backward whose gradient
