@@ -4607,6 +4607,8 @@ static int log_dropped(EvShared* s, const uint8_t* keep, int64_t dropped, unsign
 // selection must have produced: another one is DR_INTERNAL and the table
 // stays.  finish() frees the temporaries on every path; after a failed
 // begin() nothing is held.  `mark_rc` is the caller's mark step's status.
+// `log` false keeps the victims out of the removal log: a demoted key
+// (dr_ev_demote_to) leaves HBM, not the model.
 struct RemoveWs {
   uint8_t* keep = nullptr;
   unsigned long long* cnt = nullptr;
@@ -4638,7 +4640,7 @@ static int remove_begin(EvShared* s, RemoveWs* w, hipStream_t st) {
 }
 
 static int remove_finish(EvShared* s, RemoveWs* w, int mark_rc, int64_t expect, const char* what,
-                         int64_t* removed_host, hipStream_t st) {
+                         int64_t* removed_host, hipStream_t st, bool log = true) {
   const int64_t ns_ = s->cap + 1;
   int rc = mark_rc;
   unsigned long long removed = 0;
@@ -4651,7 +4653,7 @@ static int remove_finish(EvShared* s, RemoveWs* w, int mark_rc, int64_t expect, 
   }
   const bool miscount = !rc && expect >= 0 && (int64_t)removed != expect;
   if (miscount) rc = DR_INTERNAL;
-  if (s->rm_log && !rc) rc = log_dropped(s, w->keep, (int64_t)removed, w->cnt, st);
+  if (log && s->rm_log && !rc) rc = log_dropped(s, w->keep, (int64_t)removed, w->cnt, st);
   (void)hipFree(w->keep);
   (void)hipFree(w->cnt);
   if (rc) {
@@ -5175,32 +5177,49 @@ __global__ __launch_bounds__(256) void ev_budget_mark_kernel(
   }
 }
 
-}  // namespace dr
+// Where dr_ev_demote_to has the victims written before they leave the table
+// (device pointers, each nullable).  `query`: every output
+// is null, the call only counts.
+struct DemoteOut {
+  int64_t* keys;
+  void* const* values;  // host array of ncols device pointers
+  int ncols;
+  int64_t* versions;
+  int64_t* freqs;
+  uint32_t* colmask;
+  int64_t capacity;
+  bool query;
+};
 
-extern "C" {
+// (host_tier section below) writes the entries with keep == 0, keys ascending
+static int export_victims(EvShared* s, const uint8_t* keep, int64_t E, const DemoteOut& out,
+                          void* stream);
 
-int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* removed_host, void* stream) {
-  dr::EvGuard guard_(ev);
-  using namespace dr;
-  DR_REQUIRE(ev && ev->col == 0, DR_INVALID_ARGUMENT, "shrink_to needs a primary EV");
-  DR_REQUIRE(max_keys >= 0, DR_INVALID_ARGUMENT, "shrink_to: max_keys %lld < 0",
+// dr_ev_shrink_to (out == nullptr: the victims are dropped and logged) and
+// dr_ev_demote_to (the victims are exported first and not logged): one
+// selection, one removal.  *count_host: the keys evicted, or for a query the
+// keys over the budget.
+static int budget_evict(dr_ev* ev, int64_t max_keys, int policy, const DemoteOut* out,
+                        int64_t* count_host, const char* what, void* stream) {
+  DR_REQUIRE(ev && ev->col == 0, DR_INVALID_ARGUMENT, "%s needs a primary EV", what);
+  DR_REQUIRE(max_keys >= 0, DR_INVALID_ARGUMENT, "%s: max_keys %lld < 0", what,
              (long long)max_keys);
   DR_REQUIRE(policy == DR_EVICT_LRU || policy == DR_EVICT_LFU, DR_INVALID_ARGUMENT,
-             "shrink_to: unknown policy %d", policy);
+             "%s: unknown policy %d", what, policy);
   EvShared* s = ev->sh;
   DR_REQUIRE(policy != DR_EVICT_LRU || s->version, DR_INVALID_ARGUMENT,
-             "shrink_to: LRU needs the version column (steps_to_live != 0)");
+             "%s: LRU needs the version column (steps_to_live != 0)", what);
   DR_REQUIRE(policy != DR_EVICT_LFU || (s->freq && !s->bloom), DR_INVALID_ARGUMENT,
-             "shrink_to: LFU needs the freq column a Counter filter maintains");
+             "%s: LFU needs the freq column a Counter filter maintains", what);
   hipStream_t st = S(stream);
-  if (removed_host) *removed_host = 0;
+  if (count_host) *count_host = 0;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cs);
   DR_REQUIRE(cs == hipStreamCaptureStatusNone, DR_INVALID_ARGUMENT,
-             "dr_ev_shrink_to synchronises: not inside stream capture");
+             "%s synchronises: not inside stream capture", what);
   std::lock_guard<std::mutex> g(s->mu);
   DR_REQUIRE(s->cap < ((int64_t)1 << 32), DR_INVALID_ARGUMENT,
-             "shrink_to: %lld slots, the selection indexes < 2^32", (long long)s->cap);
+             "%s: %lld slots, the selection indexes < 2^32", what, (long long)s->cap);
   // a live entry owns a row below top: top bounds the gather's arrays
   int64_t top = 0;
   DR_HIP(hipStreamSynchronize(st));
@@ -5249,10 +5268,18 @@ int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* removed_ho
   DR_HIP(hipMemcpyAsync(&live, count, sizeof(live), hipMemcpyDeviceToHost, st));
   DR_HIP(hipStreamSynchronize(st));
   const int64_t N = (int64_t)live;
-  DR_REQUIRE(N <= bound, DR_INTERNAL, "shrink_to: %lld live entries over %lld rows", (long long)N,
+  DR_REQUIRE(N <= bound, DR_INTERNAL, "%s: %lld live entries over %lld rows", what, (long long)N,
              (long long)bound);
   if (N <= max_keys) return DR_OK;
   const int64_t E = N - max_keys;
+  if (out) {
+    if (out->query) {
+      if (count_host) *count_host = E;
+      return DR_OK;
+    }
+    DR_REQUIRE(out->capacity >= E, DR_INVALID_ARGUMENT, "%s: capacity %lld < %lld victims", what,
+               (long long)out->capacity, (long long)E);
+  }
   RemoveWs w;
   rc = remove_begin(s, &w, st);
   if (rc) return rc;
@@ -5267,8 +5294,380 @@ int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* removed_ho
   }
   hipLaunchKernelGGL(ev_budget_mark_kernel, dim3(tiles), dim3(256), 0, st, b.m[0], b.k[0], slot, N,
                      s->cap, state, w.keep, w.cnt);
-  return remove_finish(s, &w, hipGetLastError() == hipSuccess ? DR_OK : DR_INTERNAL, E,
-                       "dr_ev_shrink_to", removed_host, st);
+  rc = hipGetLastError() == hipSuccess ? DR_OK : DR_INTERNAL;
+  // the victims are written while the old table still holds them
+  if (!rc && out) rc = export_victims(s, w.keep, E, *out, stream);
+  return remove_finish(s, &w, rc, E, what, count_host, st, /*log=*/out == nullptr);
+}
+
+}  // namespace dr
+
+extern "C" {
+
+int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* removed_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  return dr::budget_evict(ev, max_keys, policy, nullptr, removed_host, "dr_ev_shrink_to", stream);
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// HBM + host-DRAM tier, device side.  The host store is
+// dr_host_tier.h; these three entries move keys between the tiers exactly.
+//   missing : dr_ev_missing_keys, the per-step question "which of this
+//             batch's keys are not in HBM".  Lane per key, the plain-load walk
+//             of dr_ev_remove's membership rule (ev_probe_slot_index: in the
+//             map, published, row not dead -- no first-touch bit, no Counter
+//             rule), the grouping of ev_find_kernel.  A block takes a tile of
+//             256 * kMissItems positions and reserves the places of its misses
+//             with ONE atomic add (wave ballots, wave totals in LDS).  Nothing
+//             in any table is written.
+//   demote  : dr_ev_demote_to = dr_ev_shrink_to (budget_evict, one code) whose
+//             victims are written out before the old table goes: scan of the
+//             keep bytes (ev_collect_dropped_kernel's scheme) appending
+//             (key ^ sign, row, column bits), then dr_ev_export_updated's radix
+//             sort, ev_export_meta_kernel and one dr_gather per column.
+//   promote : dr_ev_promote, the inverse.  ev_find creates each absent key;
+//             freq and version are stored as given (ev_import_kernel would
+//             clamp freq up to filter_freq and always set its column's bit);
+//             the first-touch bits become colmask, and only those columns'
+//             rows are written.  A key already in the map is left alone.
+// ===========================================================================
+namespace dr {
+
+struct MissGroup {
+  const Slot* slots[DR_MAX_GROUP];
+  int64_t cap[DR_MAX_GROUP];
+  int64_t koff[DR_MAX_GROUP + 1];
+  const int64_t* n_dev[DR_MAX_GROUP];
+};
+static_assert(sizeof(MissGroup) + 64 <= 4096, "missing-keys kernel arguments exceed 4 KiB");
+
+static constexpr int kMissItems = 8;
+
+__global__ __launch_bounds__(256) void ev_missing_keys_kernel(
+    MissGroup g, int T, const int64_t* __restrict__ keys, int64_t* __restrict__ miss_keys,
+    int64_t* __restrict__ miss_pos, unsigned long long* __restrict__ count) {
+  __shared__ const Slot* ss[DR_MAX_GROUP];
+  __shared__ int64_t sc[DR_MAX_GROUP];
+  __shared__ unsigned wtot[4];
+  __shared__ unsigned long long sbase;
+  if (threadIdx.x < T) {
+    ss[threadIdx.x] = g.slots[threadIdx.x];
+    sc[threadIdx.x] = g.cap[threadIdx.x];
+  }
+  __syncthreads();
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t total = g.koff[T];
+  const int64_t tile = (int64_t)blockIdx.x * (256 * kMissItems);
+  int64_t key[kMissItems];
+  uint64_t mask[kMissItems];  // wave-uniform
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < kMissItems; ++j) {
+    const int64_t first = tile + j * 256;
+    const int64_t i = first + threadIdx.x;
+    bool miss = false;
+    key[j] = 0;
+    if (i < total) {
+      const int t = table_of(g.koff, T, i, first);
+      const int64_t li = i - g.koff[t];
+      if (!(g.n_dev[t] && li >= *g.n_dev[t])) {
+        key[j] = gld(keys + i);
+        miss = ev_probe_slot_index(ss[t], sc[t], (uint64_t)key[j]) < 0;
+      }
+    }
+    mask[j] = __ballot(miss);
+    mine += (unsigned)__popcll(mask[j]);
+  }
+  if (lane == 0) wtot[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    sbase = t ? atomicAdd(count, (unsigned long long)t) : 0ull;
+  }
+  __syncthreads();
+  // (a miss is a position < total, and at most `total` positions miss: the
+  // outputs hold koff[T] entries)
+  int64_t pos = (int64_t)sbase;
+  for (int w = 0; w < wave; ++w) pos += wtot[w];
+#pragma unroll
+  for (int j = 0; j < kMissItems; ++j) {
+    if ((mask[j] >> lane) & 1ull) {
+      const int64_t p = pos + __popcll(mask[j] & lanemask_lt());
+      if (p < total) {
+        miss_keys[p] = key[j];
+        miss_pos[p] = tile + j * 256 + threadIdx.x;
+      }
+    }
+    pos += __popcll(mask[j]);
+  }
+}
+
+// Appends (key ^ sign, row, column bits, position) of the slots with
+// keep == 0 -- the victims the mark step chose -- one reservation per block
+// tile (ev_collect_dropped_kernel's scan; the slot is loaded only for a hit).
+__global__ __launch_bounds__(256) void ev_scan_victims_kernel(
+    const Slot* __restrict__ slots, int64_t cap, const uint8_t* __restrict__ keep,
+    uint64_t* __restrict__ kout, int64_t* __restrict__ rout, uint32_t* __restrict__ mout,
+    int32_t* __restrict__ iout, int64_t bound, unsigned long long* __restrict__ count) {
+  __shared__ unsigned wtot[4];
+  __shared__ unsigned long long sbase;
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t tile = (int64_t)blockIdx.x * (256 * kRmItems);
+  uint64_t mask[kRmItems];  // wave-uniform
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < kRmItems; ++j) {
+    const int64_t i = tile + j * 256 + threadIdx.x;
+    mask[j] = __ballot(i <= cap && gld(keep + i) == 0);
+    mine += (unsigned)__popcll(mask[j]);
+  }
+  if (lane == 0) wtot[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    sbase = t ? atomicAdd(count, (unsigned long long)t) : 0ull;
+  }
+  __syncthreads();
+  int64_t pos = (int64_t)sbase;
+  for (int w = 0; w < wave; ++w) pos += wtot[w];
+#pragma unroll
+  for (int j = 0; j < kRmItems; ++j) {
+    if ((mask[j] >> lane) & 1ull) {
+      const int64_t i = tile + j * 256 + threadIdx.x;
+      const int64_t p = pos + __popcll(mask[j] & lanemask_lt());
+      if (p < bound) {
+        const slot_v sv = gld(reinterpret_cast<const slot_v*>(slots + i));
+        kout[p] = (i < cap ? sv.x : kEmptyKey) ^ (1ull << 63);  // the special slot holds key -1
+        rout[p] = (int64_t)(sv.y & kRowMask);
+        mout[p] = (uint32_t)((sv.y >> 48) & 0xffffull);
+        iout[p] = (int32_t)p;
+      }
+    }
+    pos += __popcll(mask[j]);
+  }
+}
+
+__global__ __launch_bounds__(256) void ev_victim_colmask_kernel(const int32_t* __restrict__ is,
+                                                                const uint32_t* __restrict__ mbuf,
+                                                                int64_t m,
+                                                                uint32_t* __restrict__ colmask_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) colmask_out[i] = gld(mbuf + gld(is + i));
+}
+
+static int export_victims(EvShared* s, const uint8_t* keep, int64_t E, const DemoteOut& out,
+                          void* stream) {
+  hipStream_t st = S(stream);
+  DR_REQUIRE(E < ((int64_t)1 << 31), DR_INVALID_ARGUMENT,
+             "dr_ev_demote_to: %lld victims, the sort takes < 2^31", (long long)E);
+  const size_t sort_ws = dr_sort_pairs_workspace_size(E);
+  Carver sz(nullptr);
+  sz.take<unsigned long long>(1);
+  sz.take<uint64_t>(E);
+  sz.take<int64_t>(E);
+  sz.take<uint32_t>(E);
+  sz.take<int32_t>(E);
+  sz.take<uint64_t>(E);
+  sz.take<int32_t>(E);
+  sz.take<int64_t>(E);
+  sz.take<char>(sort_ws);
+  DevBuf buf;
+  DR_HIP(buf.alloc(sz.used + 256, st));
+  Carver c(buf.p);
+  unsigned long long* cnt = c.take<unsigned long long>(1);
+  uint64_t* kbuf = c.take<uint64_t>(E);
+  int64_t* rbuf = c.take<int64_t>(E);
+  uint32_t* mbuf = c.take<uint32_t>(E);
+  int32_t* ibuf = c.take<int32_t>(E);
+  uint64_t* ksorted = c.take<uint64_t>(E);
+  int32_t* isorted = c.take<int32_t>(E);
+  int64_t* rows = c.take<int64_t>(E);
+  char* ws = c.take<char>(sort_ws);
+  int rc = fill_bytes(cnt, 0, sizeof(unsigned long long), st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ev_scan_victims_kernel, dim3((unsigned)ceil_div(s->cap + 1, 256 * kRmItems)),
+                     dim3(256), 0, st, s->slots, s->cap, keep, kbuf, rbuf, mbuf, ibuf, E, cnt);
+  DR_LAUNCH_CHECK();
+  unsigned long long found = 0;
+  DR_HIP(hipMemcpyAsync(&found, cnt, sizeof(found), hipMemcpyDeviceToHost, st));
+  DR_HIP(hipStreamSynchronize(st));
+  DR_REQUIRE((int64_t)found == E, DR_INTERNAL, "dr_ev_demote_to: %lld victims marked of %lld",
+             (long long)found, (long long)E);
+  rc = dr_sort_pairs(kbuf, ibuf, ksorted, isorted, E, 0, 64, ws, sort_ws, stream);
+  if (rc) return rc;
+  const dim3 grid((unsigned)ceil_div(E, 256));
+  hipLaunchKernelGGL(ev_export_meta_kernel, grid, dim3(256), 0, st, ksorted, isorted, rbuf, E,
+                     s->version, s->freq, out.keys, rows, out.versions, out.freqs);
+  DR_LAUNCH_CHECK();
+  if (out.colmask) {
+    hipLaunchKernelGGL(ev_victim_colmask_kernel, grid, dim3(256), 0, st, isorted, mbuf, E,
+                       out.colmask);
+    DR_LAUNCH_CHECK();
+  }
+  for (int col = 0; col < out.ncols; ++col) {
+    if (!out.values[col]) continue;
+    rc = dr_gather(s->pools[col], s->row_cap, col_words(s, col), rows, E,
+                   static_cast<float*>(out.values[col]), stream);
+    if (rc) return rc;
+  }
+  DR_HIP(hipStreamSynchronize(st));  // the temporaries go with this call
+  return DR_OK;
+}
+
+// Find-or-create of the promoted keys, lane per key.  rows_out[i] = the row of
+// a key this lane CREATED (its columns are then written from colmask[i]), -1
+// for a key that was in the map already -- left entirely as it is -- and for
+// the later occurrences of a repeated key.
+__global__ void ev_promote_kernel(EvDesc e, const int64_t* __restrict__ keys, int64_t n,
+                                  const int64_t* __restrict__ versions,
+                                  const int64_t* __restrict__ freqs,
+                                  const uint32_t* __restrict__ colmask,
+                                  int64_t* __restrict__ rows_out, int* st) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  rows_out[i] = -1;
+  bool created;
+  uint64_t rc;
+  Slot* s = ev_find(e, (uint64_t)keys[i], true, &created, &rc, st);
+  if (!s || !created || (rc & kRowMask) == kRowDead) return;
+  const int64_t row = (int64_t)(rc & kRowMask);
+  if (e.freq) e.freq[row] = freqs ? freqs[i] : 0;           // as given: no clamp
+  if (e.version) e.version[row] = versions ? versions[i] : 0;  // -1 stays -1
+  const uint64_t bits = (uint64_t)(colmask[i] & 0xffffu) << 48;
+  if (bits) atomicOr((unsigned long long*)&s->rc, (unsigned long long)bits);
+  rows_out[i] = row;
+}
+
+struct PromoteCols {
+  float* pool[kMaxCols];
+  const float* values[kMaxCols];  // nullptr: the column is not written
+  int64_t words[kMaxCols];
+  int vec[kMaxCols];
+};
+
+// pool[c][rows[i]] = values[c][i] where rows[i] >= 0 and bit c of colmask[i]
+// is set; blockIdx.y = c, G lanes per row (ev_upsert_rows_kernel's copy).
+template <int G>
+__global__ __launch_bounds__(256) void ev_promote_rows_kernel(PromoteCols pc,
+                                                              const int64_t* __restrict__ rows,
+                                                              const uint32_t* __restrict__ colmask,
+                                                              int64_t n, int64_t row_cap) {
+  const int col = blockIdx.y;  // uniform: the column's fields are scalar loads
+  const int64_t i = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  if (i >= n || !pc.values[col]) return;
+  const int64_t r = rows[i];
+  if (r < 0 || r >= row_cap || !((gld(colmask + i) >> col) & 1u)) return;
+  const int64_t words = pc.words[col];
+  ro_copy_row<G>(pc.values[col] + i * words, pc.pool[col] + r * words, words, pc.vec[col],
+                 threadIdx.x % G);
+}
+
+}  // namespace dr
+
+extern "C" {
+
+int dr_ev_missing_keys(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                       const int64_t* koff_host, const int64_t* const* n_dev_per_table,
+                       int64_t* miss_keys_out, int64_t* miss_pos_out, int64_t* count_dev,
+                       void* stream) {
+  using namespace dr;
+  const int T = num_tables;
+  DR_REQUIRE(evs && koff_host && count_dev && T >= 1 && T <= DR_MAX_GROUP, DR_INVALID_ARGUMENT,
+             "bad argument");
+  for (int t = 0; t < T; ++t) {
+    DR_REQUIRE(evs[t], DR_INVALID_ARGUMENT, "null ev %d", t);
+    DR_REQUIRE(koff_host[t] >= 0 && koff_host[t + 1] >= koff_host[t], DR_INVALID_ARGUMENT,
+               "koff must be non-decreasing from >= 0");
+  }
+  const int64_t total = koff_host[T];
+  DR_REQUIRE(total == 0 || (keys && miss_keys_out && miss_pos_out), DR_INVALID_ARGUMENT,
+             "null keys / outputs");
+  hipStream_t st = S(stream);
+  EvGuard guard_(evs, T);
+  int rc = fill_bytes(count_dev, 0, sizeof(int64_t), st);
+  if (rc || total == 0) return rc;
+  MissGroup g;
+  memset(&g, 0, sizeof(g));
+  for (int t = 0; t < T; ++t) {
+    g.slots[t] = evs[t]->sh->slots;
+    g.cap[t] = evs[t]->sh->cap;
+    g.koff[t] = koff_host[t];
+    g.n_dev[t] = n_dev_per_table ? n_dev_per_table[t] : nullptr;
+  }
+  g.koff[T] = total;
+  hipLaunchKernelGGL(ev_missing_keys_kernel, dim3((unsigned)ceil_div(total, 256 * kMissItems)),
+                     dim3(256), 0, st, g, T, keys, miss_keys_out, miss_pos_out,
+                     reinterpret_cast<unsigned long long*>(count_dev));
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+int dr_ev_demote_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* keys_out,
+                    void* const* values_out, int ncols, int64_t* versions_out, int64_t* freqs_out,
+                    uint32_t* colmask_out, int64_t capacity, int64_t* m_host, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && ev->col == 0, DR_INVALID_ARGUMENT, "dr_ev_demote_to needs a primary EV");
+  DR_REQUIRE(ncols >= 0 && ncols <= kMaxCols && (ncols == 0 || values_out), DR_INVALID_ARGUMENT,
+             "dr_ev_demote_to: %d value columns", ncols);
+  DemoteOut out = {keys_out, values_out, ncols, versions_out, freqs_out, colmask_out, capacity,
+                   false};
+  bool any_values = false;
+  for (int c = 0; c < ncols; ++c) {
+    DR_REQUIRE(!values_out[c] || ev->sh->pools[c], DR_INVALID_ARGUMENT,
+               "dr_ev_demote_to: the key space has no column %d", c);
+    any_values = any_values || values_out[c];
+  }
+  out.query = !keys_out && !any_values && !versions_out && !freqs_out && !colmask_out;
+  return budget_evict(ev, max_keys, policy, &out, m_host, "dr_ev_demote_to", stream);
+}
+
+int dr_ev_promote(dr_ev* ev, const int64_t* keys, int64_t n, const void* const* values, int ncols,
+                  const int64_t* versions, const int64_t* freqs, const uint32_t* colmask,
+                  void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && ev->col == 0, DR_INVALID_ARGUMENT, "dr_ev_promote needs a primary EV");
+  DR_REQUIRE(n >= 0 && ncols >= 0 && ncols <= kMaxCols && (ncols == 0 || values),
+             DR_INVALID_ARGUMENT, "bad argument");
+  if (n == 0) return DR_OK;
+  DR_REQUIRE(keys && colmask, DR_INVALID_ARGUMENT, "null keys / colmask");
+  EvShared* s = ev->sh;
+  PromoteCols pc;
+  memset(&pc, 0, sizeof(pc));
+  int last = 0;  // columns [0, last) have rows to write
+  for (int c = 0; c < ncols; ++c) {
+    if (!values[c]) continue;
+    DR_REQUIRE(s->pools[c], DR_INVALID_ARGUMENT, "dr_ev_promote: the key space has no column %d",
+               c);
+    last = c + 1;
+  }
+  hipStream_t st = S(stream);
+  int rc = reserve(s, n, st);
+  if (rc) return rc;
+  // (after reserve: a growth replaces the pools)
+  for (int c = 0; c < last; ++c) {
+    if (!values[c]) continue;
+    pc.pool[c] = s->pools[c];
+    pc.values[c] = static_cast<const float*>(values[c]);
+    pc.words[c] = col_words(s, c);
+    pc.vec[c] = pc.words[c] % 4 == 0 && ((uintptr_t)pc.values[c] | (uintptr_t)pc.pool[c]) % 16 == 0;
+  }
+  int64_t* rows = nullptr;
+  DR_HIP(hipMallocAsync((void**)&rows, n * sizeof(int64_t), st));
+  EvDesc e = make_desc(ev);
+  hipLaunchKernelGGL(ev_promote_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, e, keys,
+                     n, versions, freqs, colmask, rows, status_word());
+  if (last)
+    hipLaunchKernelGGL((ev_promote_rows_kernel<16>), dim3((unsigned)ceil_div(n, 16), (unsigned)last),
+                       dim3(256), 0, st, pc, rows, colmask, n, s->row_cap);
+  const bool launched = hipGetLastError() == hipSuccess;
+  DR_HIP(hipFreeAsync(rows, st));
+  DR_REQUIRE(launched, DR_INTERNAL, "dr_ev_promote: kernel launch failed");
+  post_call(s, st);
+  return DR_OK;
 }
 
 }  // extern "C"

@@ -247,6 +247,17 @@ SIGNATURES = {
     "dr_ev_export_removed": (_I32, [_P, _P, _I64, _P, _P]),
     "dr_ev_clear_removed": (_I32, [_P, _P]),
     "dr_ev_shrink_to": (_I32, [_P, _I64, _I32, _P, _P]),
+    "dr_ev_missing_keys": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "dr_ev_demote_to": (_I32, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _P, _I64, _P, _P]),
+    "dr_ev_promote": (_I32, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
+    "dr_host_tier_create": (_I32, [_I32, _P, _I64, _P]),
+    "dr_host_tier_destroy": (_I32, [_P]),
+    "dr_host_tier_size": (_I32, [_P, _P]),
+    "dr_host_tier_put": (_I32, [_P, _P, _I64, _P, _P, _P, _P]),
+    "dr_host_tier_take": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "dr_host_tier_remove": (_I32, [_P, _P, _I64, _P]),
+    "dr_host_tier_shrink": (_I32, [_P, _I64, _I64, _P]),
+    "dr_host_tier_export": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _P]),
     "dr_ev_key_meta": (_I32, [_P, _P, _I64, _P, _P, _P, _P]),
     "dr_ev_apply_sgd": (_I32, [_P, _F32, _P, _P, _I64, _P, _I64, _P]),
     "dr_ev_apply_adagrad": (_I32, [_P, _P, _F32, _P, _P, _I64, _P, _I64, _P]),

@@ -511,7 +511,12 @@ def save(prefix, variables, global_step=None, compact=False):
             ev.shrink(0 if global_step is None else global_step)
         if p.max_keys > 0 and id(p) not in budgeted:
             budgeted.add(id(p))
-            p.shrink_to(p.max_keys, p.policy)
+            if p.tiered:
+                # HBM_DRAM: the keys over the budget go to the host tier, not away, and
+                # the dump below (export() merges both tiers) writes them all
+                p.demote_to(p.max_keys, p.policy, compact=False)
+            else:
+                p.shrink_to(p.max_keys, p.policy)
         if compact and id(p) not in compacted:
             compacted.add(id(p))
             p.compact()
@@ -594,10 +599,16 @@ def restore_embedding_variable(ev, reader, name, partition_id=0, partition_num=1
 
 
 def restore(prefix, variables, partition_id=0, partition_num=1):
-    """Restore {tensor_key: EmbeddingVariable} from a bundle."""
+    """Restore {tensor_key: EmbeddingVariable} from a bundle.  A key space with
+    a host-DRAM tier (StorageType.HBM_DRAM) ends within its HBM budget: once
+    all its variables are in, the keys over it are demoted."""
     r = BundleReader(prefix)
     for name in variables:
         restore_embedding_variable(variables[name], r, name, partition_id, partition_num)
+    tiered = {id(ev._primary or ev): (ev._primary or ev) for ev in variables.values()
+              if ev.tiered}
+    for p in tiered.values():
+        p.demote_to()
 
 
 # -- incremental checkpoints (build-defined; DESIGN section 12) ----------------
@@ -630,7 +641,11 @@ def save_incremental(prefix, variables, global_step=None):
     primary of such a key space must be among `variables`.  A key space that
     does not log removals gets neither tensor and its delta carries no
     evictions: an evicted key is simply absent from it, and a replica drops
-    it at its next full restore.  Returns `prefix`."""
+    it at its next full restore.  A key space with a host-DRAM tier is
+    refused before anything is shrunk, as its track_updates() is.  Returns
+    `prefix`."""
+    for ev in variables.values():
+        ev._refuse_tiered("save_incremental")
     w = BundleWriter(prefix)
     spaces = {}
     for ev in variables.values():
@@ -678,7 +693,10 @@ def restore_incremental(prefix, variables, partition_id=0, partition_num=1, comp
     default as the trainer's fresh row does.  compact=True compacts each
     distinct key space once at the end (EmbeddingVariable.compact), which is
     what keeps a replica fed by deltas alone bounded.  A delta without the
-    removed_* tensors restores as before."""
+    removed_* tensors restores as before.  A key space with a host-DRAM tier
+    is refused, as its track_updates() is."""
+    for ev in variables.values():
+        ev._refuse_tiered("restore_incremental")
     r = BundleReader(prefix)
     sfx = "-" + INCR_SUFFIX + "removed_keys"
     for name in variables:

@@ -18,7 +18,7 @@ import torch
 from . import _lib, ops
 from ._lib import COMBINERS, ORDER_ALI, ORDER_SEQ, DrPoolDesc, check, lib, ptr, stream_handle, workspace
 from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
-                               read_only_active)
+                               promote_grouped, read_only_active, tier_hits)
 
 
 class SparseTensor(object):
@@ -134,6 +134,33 @@ class _Feature(object):
         return self._seg32
 
 
+def _tiered_feats(feats):
+    """The features over an EmbeddingVariable whose host-DRAM tier holds keys
+    (StorageType.HBM_DRAM): none, without any launch, when every tier is empty."""
+    return [f for f in feats if isinstance(f.params, EmbeddingVariable) and f.params.tier_count()]
+
+
+def _promote_feats(feats):
+    """Before a lookup that may create keys: the ids the host tier holds come
+    back into HBM first (one dr_ev_missing_keys over the group's tiered EVs),
+    then the lookup runs as for any EV."""
+    tf = _tiered_feats(feats)
+    if tf:
+        promote_grouped([f.params for f in tf], [f.values for f in tf])
+
+
+def _refuse_tier_hits(feats):
+    """The pooled read-only paths read rows out of the EVs' pools by index, so
+    a row in the host tier cannot be served: a batch that names one raises."""
+    tf = _tiered_feats(feats)
+    n = tier_hits([f.params for f in tf], [f.values for f in tf]) if tf else 0
+    if n:
+        raise _lib.InvalidArgumentError(
+            _lib.INVALID_ARGUMENT, "read-only pooled lookup: %d id(s) of the batch are in the "
+            "host-DRAM tier of %s; promote(keys) first (sparse_read(read_only=True) serves them "
+            "in place)" % (n, ", ".join(sorted({f.params.name for f in tf}))))
+
+
 def _is_onehot(sp_ids, nnz):
     return len(sp_ids.dense_shape) == 2 and sp_ids.dense_shape[1] == 1 and \
         nnz == sp_ids.dense_shape[0]
@@ -171,7 +198,8 @@ def _prepare(f, need_unique):
         with_counts = p.filter_freq != 0          # embedding_ops.py:592-596
         f.uniq, f.idx, cnt, f.U = ops.unique_device(f.values, with_counts)
         f.defaults = p._defaults_for(f.uniq.numel(), None)
-        f.rows = p.resolve(f.uniq, n_dev=f.U, counts=cnt, defaults=f.defaults)
+        # (_run / embedding_stack promoted the group's keys: no second probe per feature)
+        f.rows = p._resolve(f.uniq, f.U, cnt, f.defaults)
     elif need_unique:
         f.uniq, f.idx, _, f.U = ops.unique_device(f.values)
 
@@ -350,6 +378,7 @@ def embedding_stack(x0, params_list, sp_ids_list, combiner="sum"):
         B, D = x0.shape
         emb = _run_readonly(feats, ORDER_ALI, None)
         return torch.cat([x0.float().unsqueeze(1), emb.view(B, len(feats), D)], 1)
+    _promote_feats(feats)
     need_grad = torch.is_grad_enabled()
     if _groupable(feats):
         _prepare_group(feats, need_grad)
@@ -921,6 +950,7 @@ def _run_readonly(feats, order, out_dtype):
                 parts[id(f)] = res[:, col:col + d]
                 col += d
         return torch.cat([parts[id(f)] for f in feats], 1)
+    _refuse_tier_hits(feats)
     with torch.no_grad():
         if _FUSED_ONEHOT:
             out = _fused_onehot_readonly(feats, order, out_dtype)
@@ -936,6 +966,7 @@ def _run(feats, order=ORDER_ALI, need_grad=None, out_dtype=None, _plain=False):
     if (not _plain and read_only_active()
             and any(isinstance(f.params, EmbeddingVariable) for f in feats)):
         return _run_readonly(feats, order, out_dtype)
+    _promote_feats(feats)
     tensors =_trainable_tensors(feats) if torch.is_grad_enabled() else []
     if need_grad is None:
         need_grad = torch.is_grad_enabled() and (
@@ -1171,6 +1202,7 @@ def _ev_sparse_read(ev, ids, counts, defaults):
     block (or None = the EV's default row)."""
     if read_only_active():
         return ev._sparse_read_readonly(ids, defaults=defaults)
+    ev.promote(ids)
     n = ids.numel()
     out = torch.empty((n, ev.dim), dtype=torch.float32, device=ev.device)
     cnt = None if counts is None else counts.to(torch.int32).contiguous()

@@ -61,12 +61,35 @@ class KeyBudgetEvict(object):
         self.steps_to_live = steps_to_live
 
 
+class StorageType(object):
+    """Where an EmbeddingVariable keeps its keys (config.proto StorageType;
+    the tiers below DRAM are not built)."""
+    HBM = "HBM"
+    HBM_DRAM = "HBM_DRAM"
+
+
+class StorageOption(object):
+    """StorageType.HBM_DRAM (build-defined): the keys a
+    KeyBudgetEvict budget pushes out of HBM are demoted to host DRAM with
+    their rows, optimizer slots, version, freq and admission state, and a
+    lookup that names one promotes it back first -- the table trains as an
+    unbudgeted one in HBM would."""
+
+    def __init__(self, storage_type=StorageType.HBM):
+        if storage_type not in (StorageType.HBM, StorageType.HBM_DRAM):
+            raise ValueError("StorageOption: storage_type is StorageType.HBM or "
+                             "StorageType.HBM_DRAM, not %r" % (storage_type,))
+        self.storage_type = storage_type
+
+
 class EmbeddingVariableOption(object):
-    def __init__(self, ht_type="", ht_partition_num=1000, evict_option=None, filter_option=None):
+    def __init__(self, ht_type="", ht_partition_num=1000, evict_option=None, filter_option=None,
+                 storage_option=None):
         self.ht_type = ht_type
         self.ht_partition_num = ht_partition_num
         self.evict_option = evict_option
         self.filter_option = filter_option
+        self.storage_option = storage_option
 
 
 def _default_row(initializer, dim, device, dtype=torch.float32):
@@ -343,6 +366,28 @@ class EmbeddingVariable(object):
         self.policy = getattr(opt.evict_option, "policy", "lru")
         # EmbeddingConfig::l2_weight_threshold (embedding_config.h:17,28): -1 = off
         self.l2_weight_threshold = float(l2_weight_threshold)
+        # host-DRAM tier of the key space (held by the primary): the store's
+        # handle, the columns it was made for and a host mirror of its size,
+        # so that an empty tier costs the lookups nothing
+        so = opt.storage_option
+        self._tiered = _primary is None and so is not None and \
+            so.storage_type == StorageType.HBM_DRAM
+        self._tier = None
+        self._tier_ncols = 0
+        self._tier_n = 0
+        if self._tiered:
+            why = None
+            if not self.max_keys:
+                why = "a KeyBudgetEvict with max_keys > 0 (the HBM budget)"
+            elif isinstance(f, CBFFilter) or getattr(f, "max_element_size", 0):
+                why = "no Bloom filter (its counters do not travel with a key)"
+            elif key_dtype != torch.int64:
+                why = "int64 keys"
+            elif self.l2_weight_threshold != -1.0:
+                why = "l2_weight_threshold == -1 (the L2 rule would need the demoted rows in HBM)"
+            if why:
+                raise _lib.InvalidArgumentError(
+                    _lib.INVALID_ARGUMENT, "StorageType.HBM_DRAM needs %s (%s)" % (why, name))
         _flush_deferred_releases()
         bf16 = self.value_dtype == torch.bfloat16
         # the C ABI takes the default row in fp32 (a bf16 EV rounds it to
@@ -378,6 +423,9 @@ class EmbeddingVariable(object):
             if getattr(self, "_h", None):
                 _release_handle(self._h)
                 self._h = None
+            if getattr(self, "_tier", None):    # host memory only: no device call
+                lib().dr_host_tier_destroy(self._tier)
+                self._tier = None
         except Exception:
             pass
 
@@ -452,6 +500,8 @@ class EmbeddingVariable(object):
         callable initializer is not called."""
         if read_only or read_only_active():
             return self._sparse_read_readonly(indices, ev_init_value)
+        if (self._primary or self)._tier_n:
+            self.promote(indices)
         i32 = indices.dtype == torch.int32
         ids = indices.reshape(-1).to(torch.int32 if i32 else torch.int64).contiguous()
         n = ids.numel()
@@ -478,6 +528,12 @@ class EmbeddingVariable(object):
         # (the C entry takes int64 keys: int32 ids are widened here)
         ids = indices.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
         n = ids.numel()
+        if n and (self._primary or self)._tier_n and _capturing():
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "a read-only lookup of an HBM_DRAM EmbeddingVariable "
+                "whose host tier holds keys cannot be captured in a graph: the rows of the ids "
+                "the tier holds are read on the host at every call (run the lookup outside the "
+                "capture, or capture while the tier is empty)")
         out = torch.empty((n, self.dim), dtype=self.value_dtype, device=self.device)
         if n:
             if defaults is None and ev_init_value is not None:
@@ -487,12 +543,16 @@ class EmbeddingVariable(object):
                                               stream_handle(self.device)))
             from .ops import _post
             _post(self.device)
+            p = self._primary or self
+            if p._tier_n:       # demoted keys are served their rows from the host tier
+                with p._lock:
+                    self._tier_patch_readonly(ids, out)
         return out.reshape(tuple(indices.shape) + (self.dim,))
 
     def find(self, keys, n_dev=None):
         """Read-only resolve of keys to rows: -(i+1) = serve the default for
         key i (absent, not admitted, or this column untouched).  The EV is
-        left exactly as it was."""
+        left exactly as it was.  HBM only: a key in the host tier is absent."""
         keys = keys.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
         n = keys.numel()
         rows = torch.empty(n, dtype=torch.int64, device=self.device)
@@ -506,6 +566,13 @@ class EmbeddingVariable(object):
     def resolve(self, keys, n_dev=None, counts=None, defaults=None):
         """Insert-on-miss resolve of (unique) keys to rows; -(i+1) = default row i."""
         keys = keys.reshape(-1).to(torch.int64).contiguous()
+        if (self._primary or self)._tier_n:
+            promote_grouped([self], [keys], [n_dev])
+        return self._resolve(keys, n_dev, counts, defaults)
+
+    def _resolve(self, keys, n_dev, counts, defaults):
+        """resolve() of contiguous int64 keys, without the promotion (the
+        grouped lookups promote once for all their features)."""
         n = keys.numel()
         rows = torch.empty(n, dtype=torch.int64, device=self.device)
         wsb = lib().dr_ev_resolve_workspace_size(n)
@@ -527,6 +594,8 @@ class EmbeddingVariable(object):
         i32 = keys.dtype == torch.int32
         k = keys.reshape(-1).to(device=self.device,
                                 dtype=torch.int32 if i32 else torch.int64).contiguous()
+        if (self._primary or self)._tier_n:
+            self.promote(k)     # an insert keeps the row of a key the model holds
         v = values.reshape(k.numel(), self.dim).to(device=self.device,
                                                    dtype=self.value_dtype).contiguous()
         ver = None if versions is None else versions.to(device=self.device,
@@ -542,7 +611,8 @@ class EmbeddingVariable(object):
                                            int(seed), stream_handle(self.device)))
 
     def total_count(self):
-        """KvVariableShape: [num keys, dim]."""
+        """KvVariableShape: [num keys, dim].  On a tiered key space the keys in
+        HBM only (tier_count() has the host tier's)."""
         n = C.c_int64(0)
         check(lib().dr_ev_size(self._h, C.byref(n), stream_handle(self.device)))
         return torch.tensor([n.value, self.dim], dtype=torch.int64)
@@ -565,7 +635,34 @@ class EmbeddingVariable(object):
             vers = vers[:0]
         if self.filter_freq == 0:
             frqs = frqs[:0]
+        p = self._primary or self
+        if p._tier_n:
+            return self._export_merged(keys[:n], vals[:n], vers, frqs)
         return keys[:n], vals[:n], vers, frqs
+
+    def _export_merged(self, keys, vals, vers, frqs):
+        """export() of a tiered key space: HBM's entries and the host tier's
+        under the same rule (the primary's and this column's first-touch bit),
+        as one list, keys ascending."""
+        import numpy as np
+        p = self._primary or self
+        col = self._slot_index
+        with p._lock:
+            tk, tv, tve, tfr, tcm = p._tier_export(columns=(col,))
+        need = np.uint32(1 | (1 << col))
+        sel = np.nonzero((tcm & need) == need)[0]
+        if col >= p._tier_ncols or sel.size == 0:
+            return keys, vals, vers, frqs
+        dev = self.device
+        rows = torch.from_numpy(tv[col][sel]).to(dev).view(self.value_dtype).reshape(-1, self.dim)
+        k2 = torch.cat([keys, torch.from_numpy(tk[sel]).to(dev)])
+        k2, order = torch.sort(k2)
+        v2 = torch.cat([vals, rows]).index_select(0, order)
+        if vers.numel() or self.steps_to_live:
+            vers = torch.cat([vers, torch.from_numpy(tve[sel]).to(dev)]).index_select(0, order)
+        if frqs.numel() or self.filter_freq:
+            frqs = torch.cat([frqs, torch.from_numpy(tfr[sel]).to(dev)]).index_select(0, order)
+        return k2, v2, vers, frqs
 
     # -- incremental checkpoints (build-defined; DESIGN section 12) -----------
     def _require_int64_keys(self, what):
@@ -584,6 +681,7 @@ class EmbeddingVariable(object):
         probe of the key table, and a fused SGD group stays fused; the same
         bits.  The flag holds until the next track_updates call."""
         self._require_int64_keys("track_updates")
+        self._refuse_tiered("track_updates")
         check(lib().dr_ev_track_updates(self._h, 1 if on else 0, stream_handle(self.device)))
         p = self._primary or self
         p._tracking = bool(on)
@@ -653,6 +751,8 @@ class EmbeddingVariable(object):
     def _upsert(self, keys, values, versions, freqs, pid, pnum):
         self._require_int64_keys("upsert")
         k = keys.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        if (self._primary or self)._tier_n:
+            self.promote(k)     # the other columns, version rules and freq of the key stay
         v = values.reshape(k.numel(), self.dim).to(device=self.device,
                                                    dtype=self.value_dtype).contiguous()
         ver = None if versions is None else versions.to(device=self.device,
@@ -662,7 +762,8 @@ class EmbeddingVariable(object):
                                  stream_handle(self.device)))
 
     def key_meta(self, keys):
-        """(freq, version, has_row) of keys, host numpy (tests/debug)."""
+        """(freq, version, has_row) of keys, host numpy (tests/debug).  HBM
+        only: a key in the host tier has no row."""
         import numpy as np
         k = np.ascontiguousarray(keys, dtype=np.int64)
         n = k.shape[0]
@@ -684,6 +785,13 @@ class EmbeddingVariable(object):
         n = C.c_int64(0)
         check(lib().dr_ev_shrink(p._h, int(global_step), p.l2_weight_threshold, C.byref(n),
                                  stream_handle(self.device)))
+        if p._tier_n and p.steps_to_live > 0:   # the age rule on the host tier's keys too
+            with p._lock:
+                t = C.c_int64(0)
+                check(lib().dr_host_tier_shrink(p._tier, int(global_step), p.steps_to_live,
+                                                C.byref(t)))
+                p._tier_n -= t.value
+            return n.value + t.value
         return n.value
 
     def compact(self):
@@ -705,7 +813,8 @@ class EmbeddingVariable(object):
 
     def rows_allocated(self):
         """Rows allocated in the key space (the device row counter):
-        total_count()[0] plus the rows of evicted keys not yet compacted."""
+        total_count()[0] plus the rows of evicted keys not yet compacted.
+        HBM only: the host tier's keys hold no row."""
         n = C.c_int64(0)
         check(lib().dr_ev_rows_allocated(self._h, C.byref(n), stream_handle(self.device)))
         return n.value
@@ -729,6 +838,9 @@ class EmbeddingVariable(object):
         k = keys.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
         n = C.c_int64(0)
         check(lib().dr_ev_remove(p._h, ptr(k), k.numel(), C.byref(n), stream_handle(self.device)))
+        if p._tier_n:       # a key lives in one tier: the counts add up
+            with p._lock:
+                return n.value + p._tier_remove(k)
         return n.value
 
     def shrink_to(self, max_keys, policy="lru"):
@@ -740,7 +852,9 @@ class EmbeddingVariable(object):
         allocated until compact() and the removal log gets them.  At or under
         the budget nothing changes.  Returns the keys removed.  A queued
         gradient (pending_grads of the primary or a slot EV) is refused, as in
-        remove(): its recorded rows would refer to dead keys."""
+        remove(): its recorded rows would refer to dead keys.  HBM only, also
+        on a tiered key space: the victims are dropped, not demoted
+        (demote_to), and the host tier is not looked at."""
         self._require_int64_keys("shrink_to")
         if policy not in _EVICT_POLICIES:
             raise _lib.InvalidArgumentError(
@@ -762,6 +876,7 @@ class EmbeddingVariable(object):
         and remove() drop from the key space this EV shares with its slots;
         save_incremental writes the log into the delta."""
         self._require_int64_keys("track_removals")
+        self._refuse_tiered("track_removals")
         check(lib().dr_ev_track_removals(self._h, 1 if on else 0, stream_handle(self.device)))
 
     def tracking_removals(self):
@@ -787,6 +902,208 @@ class EmbeddingVariable(object):
 
     def clear_removed(self):
         check(lib().dr_ev_clear_removed(self._h, stream_handle(self.device)))
+
+    # -- HBM + host-DRAM tier (build-defined) ---------------
+    @property
+    def tiered(self):
+        """Whether the key space this EV shares with its slots has a host-DRAM
+        tier (StorageOption(StorageType.HBM_DRAM) on the primary)."""
+        return (self._primary or self)._tiered
+
+    def tier_count(self):
+        """Keys held in the host-DRAM tier (0 for an untiered EV).  Host side."""
+        return (self._primary or self)._tier_n
+
+    def _refuse_tiered(self, what):
+        # a demoted row's update bit, and a demotion that is no removal, would
+        # have to travel with the key: incremental checkpoints of a tiered key
+        # space are not built
+        if self.tiered:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "%s: %s has a host-DRAM tier (StorageType.HBM_DRAM); "
+                "incremental checkpoints of a tiered key space are not supported"
+                % (what, self.name))
+
+    def _require_tiered(self, what):
+        if not self.tiered:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "%s needs StorageOption(StorageType.HBM_DRAM) (%s)"
+                % (what, self.name))
+
+    def _columns(self):
+        """The key space's columns by index (None where no slot EV exists)."""
+        p = self._primary or self
+        cols = [None] * p._next_slot
+        cols[0] = p
+        for ev in p._slots.values():
+            cols[ev._slot_index] = ev
+        return cols
+
+    @staticmethod
+    def _col_bytes(ev):
+        return 0 if ev is None else ev.dim * torch.empty(0, dtype=ev.value_dtype).element_size()
+
+    def _tier_store(self, cols):
+        """The primary's host store, made for (at least) the columns `cols`.
+        Slots created after the store move it to a wider one: their column is
+        untouched for every key it holds."""
+        n = len(cols)
+        if self._tier is not None and self._tier_ncols >= n:
+            return self._tier
+        t = C.c_void_p()
+        cb = (C.c_int64 * n)(*[self._col_bytes(ev) for ev in cols])
+        check(lib().dr_host_tier_create(n, cb, self._tier_n, C.byref(t)))
+        if self._tier is not None:
+            k, vals, ve, fr, cm = self._tier_export(self._tier_ncols)
+            ptrs = (C.c_void_p * n)(*[v.ctypes.data if v is not None else None for v in vals]
+                                    + [None] * (n - self._tier_ncols))
+            check(lib().dr_host_tier_put(t, k.ctypes.data, k.size, ptrs, ve.ctypes.data,
+                                         fr.ctypes.data, cm.ctypes.data))
+            check(lib().dr_host_tier_destroy(self._tier))
+        self._tier, self._tier_ncols = t, n
+        return t
+
+    def _tier_export(self, ncols=None, columns=None):
+        """(keys, [values per column], versions, freqs, colmask) of the store,
+        host numpy, keys ascending; values only of `columns` (default: all)."""
+        import numpy as np
+        ncols = self._tier_ncols if ncols is None else ncols
+        cols = self._columns()
+        m = self._tier_n
+        k = np.empty(m, np.int64)
+        ve, fr, cm = np.empty(m, np.int64), np.empty(m, np.int64), np.empty(m, np.uint32)
+        vals = [np.empty((m, self._col_bytes(cols[c])), np.uint8)
+                if cols[c] is not None and (columns is None or c in columns) else None
+                for c in range(ncols)]
+        ptrs = (C.c_void_p * max(ncols, 1))(*[v.ctypes.data if v is not None else None
+                                              for v in vals])
+        got = C.c_int64(0)
+        check(lib().dr_host_tier_export(self._tier, k.ctypes.data, ptrs, ve.ctypes.data,
+                                        fr.ctypes.data, cm.ctypes.data, m, C.byref(got)))
+        assert got.value == m, (got.value, m)
+        return k, vals, ve, fr, cm
+
+    def demote_to(self, max_keys=None, policy=None, compact=True):
+        """Moves the coldest keys of the key space out of HBM into the
+        host-DRAM tier until HBM holds at most `max_keys` (default: the
+        KeyBudgetEvict's): exactly shrink_to's victims, by `policy`, each with
+        every column's row, its version, freq and first-touch bits, so that
+        promote() puts it back bit for bit.  The removal log does not get
+        them: a demoted key stays in the model.  compact: ends in compact(),
+        which gives the victims' rows back.  Returns the keys demoted.  A
+        queued gradient is refused, as in remove().  Call it between steps
+        (after apply_gradients, before the next forward): a forward whose
+        backward has not run has queued nothing yet, and its gradient would
+        re-create a key demoted in between as a fresh row."""
+        import numpy as np
+        self._require_tiered("demote_to")
+        p = self._primary or self
+        max_keys = p.max_keys if max_keys is None else int(max_keys)
+        policy = p.policy if policy is None else policy
+        if policy not in _EVICT_POLICIES:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "demote_to: policy is 'lru' or 'lfu', not %r" % (policy,))
+        cols = p._columns()
+        for ev in cols:
+            if ev is not None and ev.pending_grads:
+                raise _lib.InvalidArgumentError(
+                    _lib.INVALID_ARGUMENT, "demote_to: %s has %d pending gradient(s), which may "
+                    "hold rows of the keys; apply_gradients first"
+                    % (ev.name, len(ev.pending_grads)))
+        st = stream_handle(p.device)
+        pol = _EVICT_POLICIES[policy]
+        m = C.c_int64(0)
+        check(lib().dr_ev_demote_to(p._h, max_keys, pol, None, None, 0, None, None, None, 0,
+                                    C.byref(m), st))
+        E = m.value
+        if E:
+            dev = p.device
+            keys = torch.empty(E, dtype=torch.int64, device=dev)
+            vers = torch.empty(E, dtype=torch.int64, device=dev)
+            frqs = torch.empty(E, dtype=torch.int64, device=dev)
+            cmask = torch.empty(E, dtype=torch.int32, device=dev)
+            vals = [None if ev is None else torch.empty((E, ev.dim), dtype=ev.value_dtype,
+                                                        device=dev) for ev in cols]
+            n = len(cols)
+            vptr = (C.c_void_p * n)(*[ptr(v) for v in vals])
+            check(lib().dr_ev_demote_to(p._h, max_keys, pol, ptr(keys), vptr, n, ptr(vers),
+                                        ptr(frqs), ptr(cmask), E, C.byref(m), st))
+            assert m.value == E, (m.value, E)
+            hk, hv, hf, hc = keys.cpu().numpy(), vers.cpu().numpy(), frqs.cpu().numpy(), \
+                np.ascontiguousarray(cmask.cpu().numpy().view(np.uint32))
+            hvals = [None if v is None else v.contiguous().view(torch.uint8).cpu().numpy()
+                     for v in vals]
+            with p._lock:
+                t = p._tier_store(cols)
+                hptr = (C.c_void_p * p._tier_ncols)(*(
+                    [None if v is None else v.ctypes.data for v in hvals]
+                    + [None] * (p._tier_ncols - n)))
+                check(lib().dr_host_tier_put(t, hk.ctypes.data, E, hptr, hv.ctypes.data,
+                                             hf.ctypes.data, hc.ctypes.data))
+                p._tier_n += E
+        if compact:
+            self.compact()
+        return E
+
+    def promote(self, keys):
+        """Brings the keys among `keys` that the host-DRAM tier holds back into
+        HBM, exactly as they were demoted (every column's row where it had been
+        touched, version, freq, first-touch bits), and drops them from the
+        tier.  Keys in HBM already, and keys in neither tier, are left alone.
+        Returns the keys promoted.  With an empty tier, or on an untiered EV,
+        nothing is launched."""
+        p = self._primary or self
+        if not p._tier_n:
+            return 0
+        return promote_grouped([p], [keys])
+
+    def _tier_remove(self, k):
+        """remove() on the tier's side; returns the keys it dropped."""
+        if not self._tier_n:
+            return 0
+        hk = k.cpu().numpy()
+        n = C.c_int64(0)
+        check(lib().dr_host_tier_remove(self._tier, hk.ctypes.data, hk.size, C.byref(n)))
+        self._tier_n -= n.value
+        return n.value
+
+    def _tier_patch_readonly(self, ids, out):
+        """The read-only lookup's second half on a tiered key space: the rows
+        of the ids the tier holds go from the store into `out`, under the rules
+        HBM applies (this column's and the primary's first-touch bit set, and
+        for a Counter filter the stored freq >= filter_freq); neither tier
+        changes."""
+        import numpy as np
+        p = self._primary or self
+        hk = ids.cpu().numpy()
+        uniq, inv = np.unique(hk, return_inverse=True)
+        col = self._slot_index
+        nb = self._col_bytes(self)
+        hit_idx = np.empty(uniq.size, np.int64)
+        rows = np.empty((uniq.size, nb), np.uint8)
+        fr, cm = np.empty(uniq.size, np.int64), np.empty(uniq.size, np.uint32)
+        vptr = (C.c_void_p * p._tier_ncols)()
+        if col < p._tier_ncols:
+            vptr[col] = rows.ctypes.data
+        hits = C.c_int64(0)
+        check(lib().dr_host_tier_take(p._tier, uniq.ctypes.data, uniq.size, 0, hit_idx.ctypes.data,
+                                      vptr, None, fr.ctypes.data, cm.ctypes.data, C.byref(hits)))
+        h = hits.value
+        need = np.uint32(1 | (1 << col))
+        ok = (cm[:h] & need) == need
+        if p.filter_freq:
+            ok &= fr[:h] >= p.filter_freq
+        src_of_uniq = np.full(uniq.size, -1, np.int64)
+        src_of_uniq[hit_idx[:h][ok]] = np.nonzero(ok)[0]
+        src = src_of_uniq[inv.reshape(-1)]
+        pos = np.nonzero(src >= 0)[0]
+        if pos.size:
+            # rows as 32-bit words, whatever the value dtype (dr_rows_scatter moves words)
+            block = torch.from_numpy(rows[src[pos]]).to(self.device).view(torch.float32)
+            from .ops import rows_scatter
+            rows_scatter(block, torch.from_numpy(pos.astype(np.int32)).to(self.device),
+                         out.view(torch.float32))
+        return h
 
 
 def _mark_grouped(what, evs, xs, num_valid, launch):
@@ -829,6 +1146,137 @@ def mark_updated_rows_grouped(evs, rows, num_valid=None):
     _mark_grouped("mark_updated_rows", evs, rows, num_valid,
                   lambda h, T, flat, koff, nd, st:
                   lib().dr_ev_mark_updated_rows(h, T, flat, koff, 0, nd, st))
+
+
+def _tier_misses(items):
+    """dr_ev_missing_keys over `items` = [(primary EV, keys, num_valid or
+    None)] of one device, at most MAX_GROUP of them: per item the host numpy
+    keys (duplicates kept) that are not in its HBM table.  One launch and one
+    host read of the count for the whole group."""
+    dev, T = items[0][0].device, len(items)
+    ks = [k.reshape(-1).to(device=dev, dtype=torch.int64) for _, k, _ in items]
+    flat = ks[0].contiguous() if T == 1 else torch.cat(ks)
+    koff = [0]
+    for k in ks:
+        koff.append(koff[-1] + k.numel())
+    total = koff[-1]
+    if total == 0:
+        return [None] * T
+    mk = torch.empty(total, dtype=torch.int64, device=dev)
+    mp = torch.empty(total, dtype=torch.int64, device=dev)
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)
+    handles = (C.c_void_p * T)(*[ev._h.value for ev, _, _ in items])
+    nd = (C.c_void_p * T)(*[None if n is None else n.data_ptr() for _, _, n in items])
+    check(lib().dr_ev_missing_keys(handles, T, ptr(flat), (C.c_int64 * (T + 1))(*koff), nd,
+                                   ptr(mk), ptr(mp), ptr(cnt), stream_handle(dev)))
+    m = int(cnt.item())     # the step's one synchronise
+    if m == 0:
+        return [None] * T
+    hk, hp = mk[:m].cpu().numpy(), mp[:m].cpu().numpy()
+    return [hk[(hp >= koff[t]) & (hp < koff[t + 1])] for t in range(T)]
+
+
+def _tiered_items(evs, keys, num_valid):
+    """The (primary, keys, num_valid) of the EVs whose tier holds anything,
+    by device; refuses stream capture when there is one."""
+    by_dev = {}
+    for t, ev in enumerate(evs):
+        p = getattr(ev, "_primary", None) or ev
+        if getattr(p, "_tier_n", 0) and keys[t].numel():
+            by_dev.setdefault(str(p.device), []).append(
+                (p, keys[t], None if num_valid is None else num_valid[t]))
+    if by_dev and _capturing():
+        raise _lib.InvalidArgumentError(
+            _lib.INVALID_ARGUMENT, "a lookup of an HBM_DRAM EmbeddingVariable whose host tier "
+            "holds keys cannot be captured in a graph: which keys to promote is read on the "
+            "host at every call (run the lookup outside the capture, or capture while the "
+            "tier is empty)")
+    return by_dev
+
+
+def promote_grouped(evs, keys, num_valid=None):
+    """promote() over several EVs: keys[t] (the first num_valid[t] of them:
+    device int64[1]) belong to evs[t].  One dr_ev_missing_keys per device and
+    MAX_GROUP tables finds the keys that are not in HBM; the host store gives
+    up the ones it holds (take, erase) and dr_ev_promote re-inserts them.
+    EVs without a tier, or with an empty one, are left out: for them nothing
+    is launched.  Returns the keys promoted."""
+    import numpy as np
+    promoted = 0
+    for items in _tiered_items(evs, keys, num_valid).values():
+        while items:
+            chunk, items = items[:_lib.MAX_GROUP], items[_lib.MAX_GROUP:]
+            for (p, _, _), miss in zip(chunk, _tier_misses(chunk)):
+                if miss is None or miss.size == 0 or not p._tier_n:
+                    continue
+                with p._lock:
+                    cols = p._columns()[:p._tier_ncols]
+                    # which misses the store holds (brand-new keys are most of a step's
+                    # misses): the row buffers below are sized by the hits alone
+                    idx0 = np.empty(miss.size, np.int64)
+                    hits = C.c_int64(0)
+                    check(lib().dr_host_tier_take(p._tier, miss.ctypes.data, miss.size, 0,
+                                                  idx0.ctypes.data, None, None, None, None,
+                                                  C.byref(hits)))
+                    if not hits.value:
+                        continue
+                    miss = np.ascontiguousarray(miss[idx0[:hits.value]])
+                    n = miss.size
+                    ve, fr = np.empty(n, np.int64), np.empty(n, np.int64)
+                    cm = np.empty(n, np.uint32)
+                    vals = [None if ev is None else np.empty((n, p._col_bytes(ev)), np.uint8)
+                            for ev in cols]
+                    vptr = (C.c_void_p * p._tier_ncols)(*[None if v is None else v.ctypes.data
+                                                          for v in vals])
+                    idx = np.empty(n, np.int64)
+                    hits = C.c_int64(0)
+                    check(lib().dr_host_tier_take(p._tier, miss.ctypes.data, n, 1, idx.ctypes.data,
+                                                  vptr, ve.ctypes.data, fr.ctypes.data,
+                                                  cm.ctypes.data, C.byref(hits)))
+                    h = hits.value
+                    if not h:
+                        continue
+                    p._tier_n -= h
+                    dev = p.device
+                    dk = torch.from_numpy(miss[idx[:h]]).to(dev)
+                    dvals = [None if v is None else torch.from_numpy(v[:h]).to(dev) for v in vals]
+                    dptr = (C.c_void_p * p._tier_ncols)(*[ptr(v) for v in dvals])
+                    dve, dfr = torch.from_numpy(ve[:h]).to(dev), torch.from_numpy(fr[:h]).to(dev)
+                    dcm = torch.from_numpy(cm[:h].view(np.int32)).to(dev)
+                    check(lib().dr_ev_promote(p._h, ptr(dk), h, dptr, p._tier_ncols, ptr(dve),
+                                              ptr(dfr), ptr(dcm), stream_handle(dev)))
+                    promoted += h
+    return promoted
+
+
+def tier_hits(evs, keys, num_valid=None):
+    """How many of keys[t] -- distinct per EV -- the host tier of evs[t] holds;
+    neither tier changes.  0 without a launch when every tier is empty."""
+    import numpy as np
+    hits = 0
+    for items in _tiered_items(evs, keys, num_valid).values():
+        while items:
+            chunk, items = items[:_lib.MAX_GROUP], items[_lib.MAX_GROUP:]
+            for (p, _, _), miss in zip(chunk, _tier_misses(chunk)):
+                if miss is None or miss.size == 0:
+                    continue
+                h = C.c_int64(0)
+                with p._lock:
+                    check(lib().dr_host_tier_take(p._tier, miss.ctypes.data, miss.size, 0, None,
+                                                  None, None, None, None, C.byref(h)))
+                hits += h.value
+    return hits
+
+
+def refuse_tiered_evs(evs, what):
+    """For the entry points that read or create keys in HBM without promoting
+    (the sharded engines): a tiered EV would be served defaults for the keys
+    its host tier holds, so it is refused."""
+    for ev in evs or ():    # (an engine built without local EVs has none to refuse)
+        if getattr(ev, "tiered", False):
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "%s does not promote from a host-DRAM tier: %s has "
+                "StorageType.HBM_DRAM" % (what, ev.name))
 
 
 _EV_REGISTRY = {}

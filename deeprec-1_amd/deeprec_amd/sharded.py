@@ -47,6 +47,7 @@ import torch.distributed as dist
 
 from . import _lib, ops
 from ._lib import COMBINERS, ORDER_ALI, DrPoolDesc, check, lib, ptr, stream_handle, workspace
+from .kv_variable_ops import refuse_tiered_evs
 
 
 class HipLocal(object):
@@ -54,6 +55,7 @@ class HipLocal(object):
 
     def __init__(self, evs, device):
         self.evs = evs
+        refuse_tiered_evs(self.evs, "HipLocal")
         self.device = device
         self.T = len(evs)
         self.dim = evs[0].dim
@@ -202,6 +204,7 @@ class ShardedLookup(object):
 
     def __init__(self, evs, world, rank, batch, device, backend=None, group=None):
         self.evs = evs
+        refuse_tiered_evs(self.evs, "ShardedLookup")
         self.world = world
         self.rank = rank
         self.batch = batch
@@ -476,6 +479,7 @@ class NativeShardedLookup(object):
         all-to-alls at fixed capacity, `max_ids` ids per table per rank;
         no host read) -- dr_sharded_create_ex."""
         self.comm, self.evs, self.device = comm, list(evs), device
+        refuse_tiered_evs(self.evs, "NativeShardedLookup")
         self.T = len(self.evs)
         self.dim = self.evs[0].dim
         self.bf16 = self.evs[0].value_dtype == torch.bfloat16
@@ -762,6 +766,7 @@ class ReduceScatterShardedLookup(object):
 
     def __init__(self, evs, world, rank, batch, device, group=None):
         self.evs = list(evs)
+        refuse_tiered_evs(self.evs, "ReduceScatterShardedLookup")
         self.world, self.rank, self.batch = world, rank, batch
         self.device = device
         self.group = group
@@ -915,6 +920,7 @@ class XgmiShardedLookup(object):
             if e.filter_freq != 0:
                 raise ValueError("XgmiShardedLookup needs filter-free EVs")
         self.evs = evs
+        refuse_tiered_evs(self.evs, "XgmiShardedLookup")
         self.world, self.rank, self.batch = world, rank, batch
         self.device = device
         self.group = group

@@ -764,6 +764,87 @@ int dr_ev_clear_removed(dr_ev* ev, void* stream);
 int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy,
                     int64_t* removed_host /* nullable */, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* HBM + host-DRAM tier (build-defined; the role of      */
+/* DeepRec's StorageType::HBM_DRAM): the keys over the budget are demoted   */
+/* to a host store and promoted back, exactly, when a lookup names them.    */
+/* ------------------------------------------------------------------------ */
+/* Which positions of a grouped key array (dr_ev_find_grouped's grouping:   */
+/* table t owns keys[koff_host[t] .. koff_host[t + 1]), optionally cut to   */
+/* its first *n_dev_per_table[t]) hold a key that is NOT a member of its    */
+/* table, by dr_ev_remove's rule: in the map, published, row not dead.      */
+/* First-touch bits and the Counter rule are not consulted: a key in the    */
+/* map below filter_freq is not missing.  Every such position p is appended */
+/* as (miss_keys_out[j] = keys[p], miss_pos_out[j] = p); duplicates are     */
+/* kept, the order is unspecified, both outputs hold koff_host[T] entries.  */
+/* *count_dev (device int64[1], zeroed by the call) ends as their number.   */
+/* Two launches, no allocation, no synchronise, no host read; nothing in    */
+/* any table is written.                                                    */
+int dr_ev_missing_keys(dr_ev* const* evs, int num_tables, const int64_t* keys,
+                       const int64_t* koff_host, const int64_t* const* n_dev_per_table,
+                       int64_t* miss_keys_out, int64_t* miss_pos_out, int64_t* count_dev,
+                       void* stream);
+/* dr_ev_shrink_to whose victims are written out before they leave the      */
+/* table, and are NOT appended to the removal log.  The victim set, the     */
+/* policies and every refusal are dr_ev_shrink_to's (one code).  With every */
+/* output null the call only counts: *m_host = max(N - max_keys, 0),        */
+/* nothing changes.  Otherwise, with E victims: capacity < E is             */
+/* DR_INVALID_ARGUMENT and the table stays; else the device outputs         */
+/* (each nullable) receive the victims, keys ascending as signed int64:     */
+/* keys_out[E]; values_out[c] (host array of ncols device pointers) the     */
+/* row words of column c of the key space -- whatever the row holds where   */
+/* the column's first-touch bit is clear; versions_out / freqs_out raw (0   */
+/* where the EV keeps none); colmask_out[E] = the 16 first-touch bits.      */
+/* Then the victims are removed as by dr_ev_remove: dr_ev_size drops by E,  */
+/* rows stay allocated until dr_ev_compact.  *m_host = E.  Synchronises:    */
+/* refused inside stream capture.  Device temporaries: dr_ev_shrink_to's    */
+/* plus 44 B per victim and the sort's workspace.                           */
+int dr_ev_demote_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* keys_out,
+                    void* const* values_out, int ncols, int64_t* versions_out,
+                    int64_t* freqs_out, uint32_t* colmask_out, int64_t capacity,
+                    int64_t* m_host /* nullable */, void* stream);
+/* The inverse (device inputs).  A key already in the map is left entirely  */
+/* as it is; so are the later occurrences of a repeated key.  A created key */
+/* gets freq and version AS GIVEN (no clamp to filter_freq, -1 stays -1; 0  */
+/* where the array is null), its first-touch bits become colmask[i], and    */
+/* column c's row is written from values[c][i] iff bit c is set and         */
+/* values[c] is not null; a clear bit leaves the column to its next first   */
+/* touch.  Reserves capacity for n keys first, as dr_ev_upsert does.        */
+int dr_ev_promote(dr_ev* ev, const int64_t* keys, int64_t n, const void* const* values,
+                  int ncols, const int64_t* versions /* nullable */,
+                  const int64_t* freqs /* nullable */, const uint32_t* colmask, void* stream);
+
+/* The host store of the tier: int64 key -> (version, freq, colmask, one    */
+/* value row of col_bytes[c] bytes per column).  Host pointers only, no     */
+/* device is touched; not thread-safe (the caller serialises).  Every key   */
+/* value is an ordinary key.                                                */
+typedef struct dr_host_tier dr_host_tier;
+int dr_host_tier_create(int ncols, const int64_t* col_bytes, int64_t capacity_hint,
+                        dr_host_tier** out);
+int dr_host_tier_destroy(dr_host_tier* t);
+int dr_host_tier_size(dr_host_tier* t, int64_t* n);
+/* values: ncols pointers (each, and the array, nullable).  An existing key */
+/* is overwritten.                                                          */
+int dr_host_tier_put(dr_host_tier* t, const int64_t* keys, int64_t n, const void* const* values,
+                     const int64_t* versions, const int64_t* freqs, const uint32_t* colmask);
+/* The hits, compacted in input order: hit j is input position              */
+/* hit_index_out[j]; a key repeated in the input hits once, at its first    */
+/* position.  erase != 0 removes the hits.  Outputs nullable but *hits.     */
+int dr_host_tier_take(dr_host_tier* t, const int64_t* keys, int64_t n, int erase,
+                      int64_t* hit_index_out, void* const* values_out, int64_t* versions_out,
+                      int64_t* freqs_out, uint32_t* colmask_out, int64_t* hits);
+int dr_host_tier_remove(dr_host_tier* t, const int64_t* keys, int64_t n,
+                        int64_t* removed /* nullable */);
+/* dr_ev_shrink's age rule: version -1 is stamped to global_step and kept;  */
+/* global_step - version > steps_to_live is dropped.                        */
+int dr_host_tier_shrink(dr_host_tier* t, int64_t global_step, int64_t steps_to_live,
+                        int64_t* removed /* nullable */);
+/* Every entry, keys ascending as signed int64.  All outputs null: *m = the */
+/* count only.  capacity < count is DR_INVALID_ARGUMENT.                    */
+int dr_host_tier_export(dr_host_tier* t, int64_t* keys_out, void* const* values_out,
+                        int64_t* versions_out, int64_t* freqs_out, uint32_t* colmask_out,
+                        int64_t capacity, int64_t* m);
+
 /* Per-key freq / version of the primary, host-side, syncs (tests/debug).   */
 int dr_ev_key_meta(dr_ev* ev, const int64_t* keys_host, int64_t n, int64_t* freq_host,
                    int64_t* version_host, int32_t* has_row_host, void* stream);
