@@ -14,8 +14,9 @@
 //            the free list and is handed out again before the arrays grow.
 // Plain host memory, single-threaded: the caller holds the primary EV's lock.
 //
-// Header-only and host-compilable (tools/host_tier_check.cpp walks it against
-// std::map under the sanitizers; the C entries are in host_tier.hip).
+// Header-only and host-compilable (tools/host_tier_check.cpp and
+// tools/host_tier_flags_check.cpp walk it against std::map under the
+// sanitizers; the C entries are in host_tier.hip).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -111,6 +112,84 @@ class HostTier {
     }
     for (int64_t e : hit_) erase_entry(e);
     return (int64_t)hit_.size();
+  }
+
+  // shrink() with the dropped keys written to keys_out (any order; the caller
+  // sizes it for size() entries).
+  int64_t shrink_keys(int64_t global_step, int64_t steps_to_live, int64_t* keys_out) {
+    hit_.clear();
+    for (int64_t e : map_) {
+      if (e < 0) continue;
+      int64_t& ver = version_[(size_t)e];
+      if (ver == -1)
+        ver = global_step;
+      else if (global_step - ver > steps_to_live)
+        hit_.push_back(e);
+    }
+    for (size_t j = 0; j < hit_.size(); ++j) {
+      keys_out[j] = key_[(size_t)hit_[j]];
+      erase_entry(hit_[j]);
+    }
+    return (int64_t)hit_.size();
+  }
+
+  // -- colmask as a flag word: bits 0-15 are the first-
+  // touch bits, bit 16 is "updated since the last delta" (DR_TIER_UPDATED); the
+  // store treats every bit alike.
+  // Entries with (colmask & mask) == mask.
+  int64_t count_masked(uint32_t mask) const {
+    int64_t n = 0;
+    for (int64_t e : map_)
+      if (e >= 0 && (colmask_[(size_t)e] & mask) == mask) ++n;
+    return n;
+  }
+
+  // export_all narrowed to the entries count_masked(mask) counts; the caller
+  // sizes the outputs for that many.  Returns the entries written.
+  int64_t export_masked(uint32_t mask, int64_t* keys_out, void* const* values_out,
+                        int64_t* versions_out, int64_t* freqs_out, uint32_t* colmask_out) {
+    hit_.clear();
+    for (int64_t e : map_)
+      if (e >= 0 && (colmask_[(size_t)e] & mask) == mask) hit_.push_back(e);
+    std::sort(hit_.begin(), hit_.end(),
+              [this](int64_t a, int64_t b) { return key_[(size_t)a] < key_[(size_t)b]; });
+    for (size_t j = 0; j < hit_.size(); ++j) {
+      if (keys_out) keys_out[j] = key_[(size_t)hit_[j]];
+      copy_out(hit_[j], (int64_t)j, values_out, versions_out, freqs_out, colmask_out);
+    }
+    return (int64_t)hit_.size();
+  }
+
+  // colmask &= ~mask on every entry.  Returns the entries that changed.
+  int64_t clear_bits(uint32_t mask) {
+    int64_t n = 0;
+    for (int64_t e : map_) {
+      if (e < 0 || !(colmask_[(size_t)e] & mask)) continue;
+      colmask_[(size_t)e] &= ~mask;
+      ++n;
+    }
+    return n;
+  }
+
+  // colmask |= bits on each distinct key present with (colmask & require) ==
+  // require; absent keys are ignored.  Returns the distinct keys that met the
+  // requirement (whether or not their word changed).
+  int64_t or_bits(const int64_t* keys, int64_t n, uint32_t require, uint32_t bits) {
+    hit_.clear();
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t e = find(keys[i]);
+      if (e < 0 || seen_[(size_t)e]) continue;
+      seen_[(size_t)e] = 1;
+      hit_.push_back(e);
+    }
+    int64_t h = 0;
+    for (int64_t e : hit_) {
+      seen_[(size_t)e] = 0;
+      if ((colmask_[(size_t)e] & require) != require) continue;
+      colmask_[(size_t)e] |= bits;
+      ++h;
+    }
+    return h;
   }
 
   // Every entry, keys ascending as signed int64; outputs nullable, sized for

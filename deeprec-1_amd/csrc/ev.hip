@@ -4561,10 +4561,8 @@ __global__ __launch_bounds__(256) void ev_removed_emit_kernel(const uint64_t* __
   if (p < capacity) keys_out[p] = (int64_t)(gld(ks + i) ^ (1ull << 63));
 }
 
-static int log_dropped(EvShared* s, const uint8_t* keep, int64_t dropped, unsigned long long* cnt,
-                       hipStream_t st) {
-  if (dropped <= 0) return DR_OK;
-  const int64_t need = s->rm_n + dropped;
+// Room for `need` log entries; the entries held are kept.
+static int log_reserve(EvShared* s, int64_t need, hipStream_t st) {
   if (need > s->rm_cap) {  // geometric growth; grow()'s rule: synchronise, then free
     int64_t ncap = std::max<int64_t>(s->rm_cap, kRmLogInit);
     while (ncap < need) ncap *= 2;
@@ -4581,7 +4579,16 @@ static int log_dropped(EvShared* s, const uint8_t* keep, int64_t dropped, unsign
     s->rm_log = nl;
     s->rm_cap = ncap;
   }
-  int rc = fill_bytes(cnt, 0, sizeof(unsigned long long), st);
+  return DR_OK;
+}
+
+static int log_dropped(EvShared* s, const uint8_t* keep, int64_t dropped, unsigned long long* cnt,
+                       hipStream_t st) {
+  if (dropped <= 0) return DR_OK;
+  const int64_t need = s->rm_n + dropped;
+  int rc = log_reserve(s, need, st);
+  if (rc) return rc;
+  rc = fill_bytes(cnt, 0, sizeof(unsigned long long), st);
   if (rc) return rc;
   hipLaunchKernelGGL(ev_collect_dropped_kernel,
                      dim3((unsigned)ceil_div(s->cap + 1, 256 * kRmItems)), dim3(256), 0, st,
@@ -4697,6 +4704,30 @@ int dr_ev_remove(dr_ev* ev, const int64_t* keys, int64_t n, int64_t* removed_hos
                      dim3((unsigned)ceil_div(n, 256 * kRmMarkItems)), dim3(256), 0, st,
                      s->slots, s->cap, keys, n, reinterpret_cast<uint32_t*>(w.keep), w.cnt);
   return remove_finish(s, &w, DR_OK, -1, "dr_ev_remove", removed_host, st);
+}
+
+// The keys the host tier of the key space dropped (its remove / age rule) join
+// the log as dr_ev_remove's victims do: a copy behind the entries held.
+int dr_ev_log_removed(dr_ev* ev, const int64_t* keys_dev, int64_t n, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && ev->col == 0, DR_INVALID_ARGUMENT, "dr_ev_log_removed needs a primary EV");
+  DR_REQUIRE(n >= 0 && (n == 0 || keys_dev), DR_INVALID_ARGUMENT, "bad argument");
+  EvShared* s = ev->sh;
+  hipStream_t st = S(stream);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cs);
+  DR_REQUIRE(cs == hipStreamCaptureStatusNone, DR_INVALID_ARGUMENT,
+             "dr_ev_log_removed synchronises: not inside stream capture");
+  std::lock_guard<std::mutex> g(s->mu);
+  if (!s->rm_log || n == 0) return DR_OK;
+  const int64_t need = s->rm_n + n;
+  int rc = log_reserve(s, need, st);
+  if (rc) return rc;
+  DR_HIP(hipMemcpyAsync(s->rm_log + s->rm_n, keys_dev, (size_t)n * sizeof(int64_t),
+                        hipMemcpyDeviceToDevice, st));
+  s->rm_n = need;
+  return DR_OK;
 }
 
 int dr_ev_track_removals(dr_ev* ev, int on, void* stream) {
@@ -5332,6 +5363,11 @@ int dr_ev_shrink_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* removed_ho
 //             clamp freq up to filter_freq and always set its column's bit);
 //             the first-touch bits become colmask, and only those columns'
 //             rows are written.  A key already in the map is left alone.
+//   update bit: while the key space tracks updates a victim's dirty bit leaves
+//             with it in bit 16 of its colmask (DR_TIER_UPDATED) and promote
+//             sets the bit of the new row from it; the
+//             keys the host store itself drops reach the removal log through
+//             dr_ev_log_removed.
 // ===========================================================================
 namespace dr {
 
@@ -5449,12 +5485,25 @@ __global__ __launch_bounds__(256) void ev_scan_victims_kernel(
   }
 }
 
+// colmask_out[i] = victim i's first-touch bits, and DR_TIER_UPDATED iff the key
+// space tracks updates (`dirty` non-null) and the victim's row is marked: the
+// update bit leaves HBM with its key.
 __global__ __launch_bounds__(256) void ev_victim_colmask_kernel(const int32_t* __restrict__ is,
                                                                 const uint32_t* __restrict__ mbuf,
-                                                                int64_t m,
+                                                                const int64_t* __restrict__ rbuf,
+                                                                const uint32_t* __restrict__ dirty,
+                                                                int64_t row_cap, int64_t m,
                                                                 uint32_t* __restrict__ colmask_out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) colmask_out[i] = gld(mbuf + gld(is + i));
+  if (i >= m) return;
+  const int32_t j = gld(is + i);
+  uint32_t cm = gld(mbuf + j);
+  if (dirty) {
+    const int64_t row = gld(rbuf + j);
+    if (row >= 0 && row < row_cap && ((gld(dirty + (row >> 5)) >> (row & 31)) & 1u))
+      cm |= DR_TIER_UPDATED;
+  }
+  colmask_out[i] = cm;
 }
 
 static int export_victims(EvShared* s, const uint8_t* keep, int64_t E, const DemoteOut& out,
@@ -5502,8 +5551,8 @@ static int export_victims(EvShared* s, const uint8_t* keep, int64_t E, const Dem
                      s->version, s->freq, out.keys, rows, out.versions, out.freqs);
   DR_LAUNCH_CHECK();
   if (out.colmask) {
-    hipLaunchKernelGGL(ev_victim_colmask_kernel, grid, dim3(256), 0, st, isorted, mbuf, E,
-                       out.colmask);
+    hipLaunchKernelGGL(ev_victim_colmask_kernel, grid, dim3(256), 0, st, isorted, mbuf, rbuf,
+                       s->dirty, s->row_cap, E, out.colmask);
     DR_LAUNCH_CHECK();
   }
   for (int col = 0; col < out.ncols; ++col) {
@@ -5524,6 +5573,7 @@ __global__ void ev_promote_kernel(EvDesc e, const int64_t* __restrict__ keys, in
                                   const int64_t* __restrict__ versions,
                                   const int64_t* __restrict__ freqs,
                                   const uint32_t* __restrict__ colmask,
+                                  uint32_t* __restrict__ dirty, int64_t row_cap,
                                   int64_t* __restrict__ rows_out, int* st) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -5535,8 +5585,15 @@ __global__ void ev_promote_kernel(EvDesc e, const int64_t* __restrict__ keys, in
   const int64_t row = (int64_t)(rc & kRowMask);
   if (e.freq) e.freq[row] = freqs ? freqs[i] : 0;           // as given: no clamp
   if (e.version) e.version[row] = versions ? versions[i] : 0;  // -1 stays -1
-  const uint64_t bits = (uint64_t)(colmask[i] & 0xffffu) << 48;
+  const uint32_t cm = colmask[i];
+  const uint64_t bits = (uint64_t)(cm & 0xffffu) << 48;
   if (bits) atomicOr((unsigned long long*)&s->rc, (unsigned long long)bits);
+  // the update bit arrives with the key (`dirty` null: the key space is not tracking)
+  if (dirty && (cm & DR_TIER_UPDATED) && row < row_cap) {
+    uint32_t* w = dirty + (row >> 5);
+    const uint32_t m = 1u << (row & 31);
+    if (!(gld(w) & m)) atomicOr(w, m);
+  }
   rows_out[i] = row;
 }
 
@@ -5658,8 +5715,9 @@ int dr_ev_promote(dr_ev* ev, const int64_t* keys, int64_t n, const void* const* 
   int64_t* rows = nullptr;
   DR_HIP(hipMallocAsync((void**)&rows, n * sizeof(int64_t), st));
   EvDesc e = make_desc(ev);
+  // (the bitmap and row_cap read here, after reserve: a growth replaces the bitmap)
   hipLaunchKernelGGL(ev_promote_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, e, keys,
-                     n, versions, freqs, colmask, rows, status_word());
+                     n, versions, freqs, colmask, s->dirty, s->row_cap, rows, status_word());
   if (last)
     hipLaunchKernelGGL((ev_promote_rows_kernel<16>), dim3((unsigned)ceil_div(n, 16), (unsigned)last),
                        dim3(256), 0, st, pc, rows, colmask, n, s->row_cap);

@@ -96,4 +96,58 @@ int dr_host_tier_export(dr_host_tier* t, int64_t* keys_out, void* const* values_
   return DR_OK;
 }
 
+// -- colmask as a flag word: the update bit of an incremental checkpoint
+// travels in bit 16 (DR_TIER_UPDATED) -----------------------
+
+int dr_host_tier_count_masked(dr_host_tier* t, uint32_t mask, int64_t* n) {
+  DR_REQUIRE(t && n, DR_INVALID_ARGUMENT, "dr_host_tier_count_masked: null argument");
+  *n = t->t.count_masked(mask);
+  return DR_OK;
+}
+
+int dr_host_tier_export_masked(dr_host_tier* t, uint32_t mask, int64_t* keys_out,
+                               void* const* values_out, int64_t* versions_out, int64_t* freqs_out,
+                               uint32_t* colmask_out, int64_t capacity, int64_t* m) {
+  DR_REQUIRE(t && m, DR_INVALID_ARGUMENT, "dr_host_tier_export_masked: null argument");
+  *m = t->t.count_masked(mask);
+  if (!keys_out && !values_out && !versions_out && !freqs_out && !colmask_out) return DR_OK;
+  DR_REQUIRE(capacity >= *m, DR_INVALID_ARGUMENT,
+             "dr_host_tier_export_masked: capacity %lld < %lld", (long long)capacity,
+             (long long)*m);
+  DR_TIER_TRY("dr_host_tier_export_masked",
+              t->t.export_masked(mask, keys_out, values_out, versions_out, freqs_out, colmask_out));
+  return DR_OK;
+}
+
+int dr_host_tier_clear_bits(dr_host_tier* t, uint32_t mask, int64_t* changed) {
+  DR_REQUIRE(t, DR_INVALID_ARGUMENT, "dr_host_tier_clear_bits: null tier");
+  const int64_t c = t->t.clear_bits(mask);
+  if (changed) *changed = c;
+  return DR_OK;
+}
+
+int dr_host_tier_or_bits(dr_host_tier* t, const int64_t* keys, int64_t n, uint32_t require,
+                         uint32_t bits, int64_t* hit) {
+  DR_REQUIRE(t && n >= 0 && (n == 0 || keys), DR_INVALID_ARGUMENT,
+             "dr_host_tier_or_bits: bad argument");
+  int64_t h = 0;
+  DR_TIER_TRY("dr_host_tier_or_bits", h = t->t.or_bits(keys, n, require, bits));
+  if (hit) *hit = h;
+  return DR_OK;
+}
+
+int dr_host_tier_shrink_keys(dr_host_tier* t, int64_t global_step, int64_t steps_to_live,
+                             int64_t* keys_out, int64_t capacity, int64_t* removed) {
+  DR_REQUIRE(t, DR_INVALID_ARGUMENT, "dr_host_tier_shrink_keys: null tier");
+  // refused before the walk stamps a version or drops a key
+  DR_REQUIRE(capacity >= t->t.size() && (keys_out || t->t.size() == 0), DR_INVALID_ARGUMENT,
+             "dr_host_tier_shrink_keys: capacity %lld < the tier's %lld keys", (long long)capacity,
+             (long long)t->t.size());
+  int64_t r = 0;
+  DR_TIER_TRY("dr_host_tier_shrink_keys",
+              r = t->t.shrink_keys(global_step, steps_to_live, keys_out));
+  if (removed) *removed = r;
+  return DR_OK;
+}
+
 }  // extern "C"

@@ -45,6 +45,7 @@ POOL_OUT_BF16 = 4
 LOOKUP_OUT_BF16 = 1
 LOOKUP_TABLE_ORDER = 2
 LOOKUP_ROWS_RECORD = 4
+TIER_UPDATED = 1 << 16      # DR_TIER_UPDATED: the update bit in a host-tier colmask
 
 
 class DeepRecError(RuntimeError):
@@ -258,6 +259,12 @@ SIGNATURES = {
     "dr_host_tier_remove": (_I32, [_P, _P, _I64, _P]),
     "dr_host_tier_shrink": (_I32, [_P, _I64, _I64, _P]),
     "dr_host_tier_export": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _P]),
+    "dr_ev_log_removed": (_I32, [_P, _P, _I64, _P]),
+    "dr_host_tier_count_masked": (_I32, [_P, C.c_uint32, _P]),
+    "dr_host_tier_export_masked": (_I32, [_P, C.c_uint32, _P, _P, _P, _P, _P, _I64, _P]),
+    "dr_host_tier_clear_bits": (_I32, [_P, C.c_uint32, _P]),
+    "dr_host_tier_or_bits": (_I32, [_P, _P, _I64, C.c_uint32, C.c_uint32, _P]),
+    "dr_host_tier_shrink_keys": (_I32, [_P, _I64, _I64, _P, _I64, _P]),
     "dr_ev_key_meta": (_I32, [_P, _P, _I64, _P, _P, _P, _P]),
     "dr_ev_apply_sgd": (_I32, [_P, _F32, _P, _P, _I64, _P, _I64, _P]),
     "dr_ev_apply_adagrad": (_I32, [_P, _P, _F32, _P, _P, _I64, _P, _I64, _P]),

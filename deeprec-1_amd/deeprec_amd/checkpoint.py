@@ -642,8 +642,13 @@ def save_incremental(prefix, variables, global_step=None):
     does not log removals gets neither tensor and its delta carries no
     evictions: an evicted key is simply absent from it, and a replica drops
     it at its next full restore.  A key space with a host-DRAM tier is
-    refused before anything is shrunk, as its track_updates() is.  Returns
-    `prefix`."""
+    refused before anything is shrunk, as its track_updates() is, unless it
+    opted in (StorageOption(StorageType.HBM_DRAM, incremental=True); DESIGN
+    section 17).  Then the age rule runs on both tiers, the keys over the
+    budget are demoted (demote_to, compact=False: they stay in the model and
+    out of the removal log) in place of shrink_to, and the delta holds the
+    marked keys of both tiers -- the bytes an untiered, unbudgeted trainer
+    that saw the same calls writes.  Returns `prefix`."""
     for ev in variables.values():
         ev._refuse_tiered("save_incremental")
     w = BundleWriter(prefix)
@@ -660,7 +665,12 @@ def save_incremental(prefix, variables, global_step=None):
         if global_step is not None and (p.l2_weight_threshold != -1.0 or p.steps_to_live > 0):
             p.shrink(global_step)
         if p.max_keys > 0:
-            p.shrink_to(p.max_keys, p.policy)
+            if p.tiered:
+                # HBM_DRAM (opted in): the keys over the budget go to the host tier with
+                # their update bits, not away; export_updated() below merges both tiers
+                p.demote_to(p.max_keys, p.policy, compact=False)
+            else:
+                p.shrink_to(p.max_keys, p.policy)
     for name in variables:
         ev = variables[name]
         keys, vals, vers, frqs = ev.export_updated()
@@ -694,7 +704,10 @@ def restore_incremental(prefix, variables, partition_id=0, partition_num=1, comp
     distinct key space once at the end (EmbeddingVariable.compact), which is
     what keeps a replica fed by deltas alone bounded.  A delta without the
     removed_* tensors restores as before.  A key space with a host-DRAM tier
-    is refused, as its track_updates() is."""
+    is refused, as its track_updates() is, unless it opted in
+    (StorageOption(StorageType.HBM_DRAM, incremental=True)): then the removals
+    reach both tiers, an upsert promotes its keys first, and the key space
+    ends within its HBM budget (demote_to), as restore() ends."""
     for ev in variables.values():
         ev._refuse_tiered("restore_incremental")
     r = BundleReader(prefix)
@@ -724,3 +737,8 @@ def restore_incremental(prefix, variables, partition_id=0, partition_num=1, comp
             if id(p) not in done:
                 done.add(id(p))
                 p.compact()
+    # as restore() ends: a tiered key space is back within its HBM budget
+    tiered = {id(ev._primary or ev): (ev._primary or ev) for ev in variables.values()
+              if ev.tiered}
+    for p in tiered.values():
+        p.demote_to()

@@ -73,13 +73,20 @@ class StorageOption(object):
     KeyBudgetEvict budget pushes out of HBM are demoted to host DRAM with
     their rows, optimizer slots, version, freq and admission state, and a
     lookup that names one promotes it back first -- the table trains as an
-    unbudgeted one in HBM would."""
+    unbudgeted one in HBM would.  incremental=True (HBM_DRAM only; DESIGN
+    section 17) also lets the key space track updates and removals and write
+    and apply incremental checkpoints: the update bit and the removal log
+    follow a key across the tiers.  Without it those calls are refused."""
 
-    def __init__(self, storage_type=StorageType.HBM):
+    def __init__(self, storage_type=StorageType.HBM, incremental=False):
         if storage_type not in (StorageType.HBM, StorageType.HBM_DRAM):
             raise ValueError("StorageOption: storage_type is StorageType.HBM or "
                              "StorageType.HBM_DRAM, not %r" % (storage_type,))
+        if incremental and storage_type != StorageType.HBM_DRAM:
+            raise ValueError("StorageOption: incremental=True is the opt-in of a "
+                             "StorageType.HBM_DRAM key space (an HBM one needs none)")
         self.storage_type = storage_type
+        self.incremental = bool(incremental)
 
 
 class EmbeddingVariableOption(object):
@@ -375,6 +382,9 @@ class EmbeddingVariable(object):
         self._tier = None
         self._tier_ncols = 0
         self._tier_n = 0
+        # StorageOption(..., incremental=True): update bits and the removal log
+        # follow the keys across the tiers
+        self._tier_incremental = self._tiered and bool(getattr(so, "incremental", False))
         if self._tiered:
             why = None
             if not self.max_keys:
@@ -679,11 +689,17 @@ class EmbeddingVariable(object):
         by_row: apply_gradients marks from the rows the forward resolved
         (mark_updated_rows) wherever a pending gradient carries them -- no
         probe of the key table, and a fused SGD group stays fused; the same
-        bits.  The flag holds until the next track_updates call."""
+        bits.  The flag holds until the next track_updates call.  On a tiered
+        key space (StorageOption(..., incremental=True)) the demoted keys carry
+        their bit in the host store; turning tracking off, or on while it was
+        off, drops those too."""
         self._require_int64_keys("track_updates")
         self._refuse_tiered("track_updates")
-        check(lib().dr_ev_track_updates(self._h, 1 if on else 0, stream_handle(self.device)))
         p = self._primary or self
+        fresh = not (on and p._tracking)    # (on while on keeps the marks, as the device side)
+        check(lib().dr_ev_track_updates(self._h, 1 if on else 0, stream_handle(self.device)))
+        if fresh:
+            p._tier_clear_updated()
         p._tracking = bool(on)
         p._tracking_by_row = bool(on) and bool(by_row)
 
@@ -711,14 +727,64 @@ class EmbeddingVariable(object):
         mark_updated_rows_grouped([self], [rows], [num_valid])
 
     def updated_count(self):
-        """Number of marked rows: an upper bound on len(export_updated()[0])."""
+        """Number of marked rows, plus the marked keys the host tier holds: an
+        upper bound on len(export_updated()[0])."""
         n = C.c_int64(0)
         check(lib().dr_ev_updated_count(self._h, C.byref(n), stream_handle(self.device)))
+        p = self._primary or self
+        if p._tier_n:       # the marked keys the host tier holds
+            with p._lock:
+                t = C.c_int64(0)
+                check(lib().dr_host_tier_count_masked(p._tier, _lib.TIER_UPDATED, C.byref(t)))
+            return n.value + t.value
         return n.value
 
     def export_updated(self):
         """export() narrowed to the marked keys: (keys, values, versions,
-        freqs), keys ascending.  Marks are left in place (clear_updated)."""
+        freqs), keys ascending.  Marks are left in place (clear_updated).  On
+        a tiered key space the marked keys of both tiers, as export()."""
+        if (self._primary or self)._tier_n:
+            return self._export_updated_merged(*self._export_updated_hbm())
+        return self._export_updated_hbm()
+
+    def _export_updated_merged(self, keys, vals, vers, frqs):
+        """export_updated() of a tiered key space: HBM's marked entries and
+        the host tier's entries that carry the update bit, under the rule HBM
+        applies (the primary's and this column's first-touch bit), as one
+        list, keys ascending.  Only the flagged entries are read out of the
+        store (dr_host_tier_export_masked), not the tier."""
+        import numpy as np
+        p = self._primary or self
+        col = self._slot_index
+        if col >= p._tier_ncols:    # a column made after the store: untouched for its keys
+            return keys, vals, vers, frqs
+        mask = _lib.TIER_UPDATED | 1 | (1 << col)
+        with p._lock:
+            m = C.c_int64(0)
+            check(lib().dr_host_tier_count_masked(p._tier, mask, C.byref(m)))
+            M = m.value
+            if M == 0:
+                return keys, vals, vers, frqs
+            tk, tve, tfr = np.empty(M, np.int64), np.empty(M, np.int64), np.empty(M, np.int64)
+            tv = np.empty((M, self._col_bytes(self)), np.uint8)
+            vptr = (C.c_void_p * p._tier_ncols)()
+            vptr[col] = tv.ctypes.data
+            check(lib().dr_host_tier_export_masked(p._tier, mask, tk.ctypes.data, vptr,
+                                                   tve.ctypes.data, tfr.ctypes.data, None, M,
+                                                   C.byref(m)))
+            assert m.value == M, (m.value, M)
+        dev = self.device
+        rows = torch.from_numpy(tv).to(dev).view(self.value_dtype).reshape(-1, self.dim)
+        k2 = torch.cat([keys, torch.from_numpy(tk).to(dev)])
+        k2, order = torch.sort(k2)
+        v2 = torch.cat([vals, rows]).index_select(0, order)
+        if vers.numel() or self.steps_to_live:
+            vers = torch.cat([vers, torch.from_numpy(tve).to(dev)]).index_select(0, order)
+        if frqs.numel() or self.filter_freq:
+            frqs = torch.cat([frqs, torch.from_numpy(tfr).to(dev)]).index_select(0, order)
+        return k2, v2, vers, frqs
+
+    def _export_updated_hbm(self):
         self._require_int64_keys("export_updated")
         m = C.c_int64(0)
         st = stream_handle(self.device)
@@ -742,6 +808,21 @@ class EmbeddingVariable(object):
 
     def clear_updated(self):
         check(lib().dr_ev_clear_updated(self._h, stream_handle(self.device)))
+        (self._primary or self)._tier_clear_updated()
+
+    def _tier_clear_updated(self):
+        """Drops the update bit of every key the host store holds (primary)."""
+        if self._tier is not None:
+            with self._lock:
+                check(lib().dr_host_tier_clear_bits(self._tier, _lib.TIER_UPDATED, None))
+
+    def _tier_log_removed(self, hk):
+        """The keys (host numpy) the host tier dropped join the removal log of
+        the key space, as the keys HBM drops do (a no-op while not logging)."""
+        if hk.size:
+            dk = torch.from_numpy(hk).to(self.device)
+            check(lib().dr_ev_log_removed(self._h, ptr(dk), dk.numel(),
+                                          stream_handle(self.device)))
 
     def upsert(self, keys, values, versions=None, freqs=None):
         """insert() that OVERWRITES the rows of keys already present (insert
@@ -786,11 +867,22 @@ class EmbeddingVariable(object):
         check(lib().dr_ev_shrink(p._h, int(global_step), p.l2_weight_threshold, C.byref(n),
                                  stream_handle(self.device)))
         if p._tier_n and p.steps_to_live > 0:   # the age rule on the host tier's keys too
+            import numpy as np
+            gone = None
             with p._lock:
                 t = C.c_int64(0)
-                check(lib().dr_host_tier_shrink(p._tier, int(global_step), p.steps_to_live,
-                                                C.byref(t)))
+                if p._tier_incremental and p.tracking_removals():
+                    # the removal log gets the tier's victims as it got HBM's
+                    gone = np.empty(p._tier_n, np.int64)
+                    check(lib().dr_host_tier_shrink_keys(p._tier, int(global_step),
+                                                         p.steps_to_live, gone.ctypes.data,
+                                                         gone.size, C.byref(t)))
+                else:
+                    check(lib().dr_host_tier_shrink(p._tier, int(global_step), p.steps_to_live,
+                                                    C.byref(t)))
                 p._tier_n -= t.value
+            if gone is not None:
+                p._tier_log_removed(gone[:t.value])
             return n.value + t.value
         return n.value
 
@@ -839,6 +931,11 @@ class EmbeddingVariable(object):
         n = C.c_int64(0)
         check(lib().dr_ev_remove(p._h, ptr(k), k.numel(), C.byref(n), stream_handle(self.device)))
         if p._tier_n:       # a key lives in one tier: the counts add up
+            if p._tier_incremental and p.tracking_removals():
+                with p._lock:
+                    gone = p._tier_remove_keys(k)
+                p._tier_log_removed(gone)   # the tier's victims join the log as HBM's did
+                return n.value + gone.size
             with p._lock:
                 return n.value + p._tier_remove(k)
         return n.value
@@ -917,8 +1014,8 @@ class EmbeddingVariable(object):
     def _refuse_tiered(self, what):
         # a demoted row's update bit, and a demotion that is no removal, would
         # have to travel with the key: incremental checkpoints of a tiered key
-        # space are not built
-        if self.tiered:
+        # space are built only for StorageOption(..., incremental=True)
+        if self.tiered and not (self._primary or self)._tier_incremental:
             raise _lib.InvalidArgumentError(
                 _lib.INVALID_ARGUMENT, "%s: %s has a host-DRAM tier (StorageType.HBM_DRAM); "
                 "incremental checkpoints of a tiered key space are not supported"
@@ -1067,6 +1164,18 @@ class EmbeddingVariable(object):
         self._tier_n -= n.value
         return n.value
 
+    def _tier_remove_keys(self, k):
+        """_tier_remove that returns the dropped keys (host numpy): take with
+        erase and no value outputs."""
+        import numpy as np
+        hk = np.ascontiguousarray(k.cpu().numpy())
+        idx = np.empty(hk.size, np.int64)
+        hits = C.c_int64(0)
+        check(lib().dr_host_tier_take(self._tier, hk.ctypes.data, hk.size, 1, idx.ctypes.data,
+                                      None, None, None, None, C.byref(hits)))
+        self._tier_n -= hits.value
+        return np.ascontiguousarray(hk[idx[:hits.value]])
+
     def _tier_patch_readonly(self, ids, out):
         """The read-only lookup's second half on a tiered key space: the rows
         of the ids the tier holds go from the store into `out`, under the rules
@@ -1135,7 +1244,30 @@ def mark_updated_grouped(evs, keys, num_valid=None):
     """mark_updated over several EVs with one launch per device and
     MAX_GROUP tables (dr_ev_mark_updated's grouping): keys[t], and the
     optional device count num_valid[t], belong to evs[t].  EVs whose key
-    space is not tracking are left out."""
+    space is not tracking are left out.  A tracking EV whose host tier holds
+    keys also has the ones among keys[t] that the tier holds with the primary
+    bit set flagged there, as an untiered table would mark them (a host read
+    of the keys: this is the public route, not apply_gradients')."""
+    _mark_updated_hbm(evs, keys, num_valid)
+    import numpy as np
+    for t, ev in enumerate(evs):
+        p = getattr(ev, "_primary", None) or ev
+        if not (getattr(p, "_tier_n", 0) and ev.tracking_updates() and keys[t].numel()):
+            continue
+        k = keys[t].reshape(-1)
+        if num_valid is not None and num_valid[t] is not None:
+            k = k[:int(num_valid[t].item())]
+        hk = np.ascontiguousarray(k.to(torch.int64).cpu().numpy())
+        with p._lock:
+            check(lib().dr_host_tier_or_bits(p._tier, hk.ctypes.data, hk.size, 1,
+                                             _lib.TIER_UPDATED, None))
+
+
+def _mark_updated_hbm(evs, keys, num_valid=None):
+    """mark_updated_grouped on the device alone: apply_gradients' route.  The
+    keys of a pending gradient were promoted by their forward, so the host
+    tier is not consulted -- a tiered EV's step costs what an untiered one's
+    does."""
     _mark_grouped("mark_updated", evs, keys, num_valid, lib().dr_ev_mark_updated)
 
 

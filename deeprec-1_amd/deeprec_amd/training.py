@@ -15,7 +15,7 @@ from . import ops
 from ._lib import check, lib, ptr, stream_handle
 from .embedding_ops import DenseTable
 from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
-                              _flush_deferred_releases, mark_updated_grouped,
+                              _flush_deferred_releases, _mark_updated_hbm,
                               mark_updated_rows_grouped)
 
 
@@ -143,7 +143,7 @@ class _Optimizer(object):
         for items in rounds:
             self._apply_ev_batch(items, gs)
         if late:
-            mark_updated_grouped(*late)
+            _mark_updated_hbm(*late)
         self._finish()
         _flush_deferred_releases()   # EVs collected meanwhile (no-op while capturing)
 
@@ -181,8 +181,9 @@ class _Optimizer(object):
         if by_row:
             marks = [(var, sl) for var, sl in marks if not var.tracking_by_row()]
         if marks:   # one launch per device and MAX_GROUP slices
-            mark_updated_grouped([var for var, _ in marks], [sl.indices for _, sl in marks],
-                                 [sl.num_valid for _, sl in marks])
+            # (device only: a pending gradient's keys were promoted by their forward)
+            _mark_updated_hbm([var for var, _ in marks], [sl.indices for _, sl in marks],
+                              [sl.num_valid for _, sl in marks])
         if not by_row:
             return late or None
         # (after the marks by key: a group those formed is no longer fusable,
@@ -201,8 +202,8 @@ class _Optimizer(object):
             mark_updated_rows_grouped([var for var, _ in formed], [sl.rows for _, sl in formed],
                                       [sl.num_valid for _, sl in formed])
         if keyed:
-            mark_updated_grouped([var for var, _ in keyed], [sl.indices for _, sl in keyed],
-                                 [sl.num_valid for _, sl in keyed])
+            _mark_updated_hbm([var for var, _ in keyed], [sl.indices for _, sl in keyed],
+                              [sl.num_valid for _, sl in keyed])
         return late or None
 
     def _apply_fused_rows(self, var_list, gs):

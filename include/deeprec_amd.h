@@ -813,6 +813,22 @@ int dr_ev_demote_to(dr_ev* ev, int64_t max_keys, int policy, int64_t* keys_out,
 int dr_ev_promote(dr_ev* ev, const int64_t* keys, int64_t n, const void* const* values,
                   int ncols, const int64_t* versions /* nullable */,
                   const int64_t* freqs /* nullable */, const uint32_t* colmask, void* stream);
+/* The update bit of an incremental checkpoint travels with a demoted key   */
+/* in bit 16 of its colmask.  While the key space       */
+/* tracks updates (dr_ev_track_updates), dr_ev_demote_to also sets it in    */
+/* colmask_out[i] iff victim i's row is marked, and dr_ev_promote marks the */
+/* row of a key it CREATES iff the bit is set in colmask[i] -- the same     */
+/* launch, no host read.  With tracking off demote_to never sets the bit    */
+/* and promote ignores it.  The vacated row's mark stays, as after          */
+/* dr_ev_remove: it selects nothing, and dr_ev_compact clears it.           */
+#define DR_TIER_UPDATED (1u << 16)
+/* Appends the n device keys to the key space's removal log, as if          */
+/* dr_ev_remove had dropped them (duplicates are kept: dr_ev_export_removed */
+/* makes them distinct): how the keys the host tier drops reach the delta.  */
+/* The log grows as dr_ev_remove grows it.  DR_OK and nothing done when the */
+/* key space is not logging or n == 0.  Primary EV; may synchronise (a      */
+/* growth): refused inside stream capture.                                  */
+int dr_ev_log_removed(dr_ev* ev, const int64_t* keys_dev, int64_t n, void* stream);
 
 /* The host store of the tier: int64 key -> (version, freq, colmask, one    */
 /* value row of col_bytes[c] bytes per column).  Host pointers only, no     */
@@ -844,6 +860,31 @@ int dr_host_tier_shrink(dr_host_tier* t, int64_t global_step, int64_t steps_to_l
 int dr_host_tier_export(dr_host_tier* t, int64_t* keys_out, void* const* values_out,
                         int64_t* versions_out, int64_t* freqs_out, uint32_t* colmask_out,
                         int64_t capacity, int64_t* m);
+/* colmask as a flag word (bits 0-15 first touch, DR_TIER_UPDATED; the      */
+/* store treats every bit alike).  *n = the entries with                    */
+/* (colmask & mask) == mask.                                                */
+int dr_host_tier_count_masked(dr_host_tier* t, uint32_t mask, int64_t* n);
+/* dr_host_tier_export narrowed to exactly those entries, keys ascending as */
+/* signed int64: a delta reads the flagged entries, not the tier.  All      */
+/* outputs null: *m = the count only.  capacity < count is                  */
+/* DR_INVALID_ARGUMENT and nothing is written.                              */
+int dr_host_tier_export_masked(dr_host_tier* t, uint32_t mask, int64_t* keys_out,
+                               void* const* values_out, int64_t* versions_out,
+                               int64_t* freqs_out, uint32_t* colmask_out, int64_t capacity,
+                               int64_t* m);
+/* colmask &= ~mask on every entry; *changed = the entries that had a bit.  */
+int dr_host_tier_clear_bits(dr_host_tier* t, uint32_t mask, int64_t* changed /* nullable */);
+/* colmask |= bits on each distinct key present with                        */
+/* (colmask & require) == require; absent keys are ignored.  *hit = those   */
+/* keys' number.                                                            */
+int dr_host_tier_or_bits(dr_host_tier* t, const int64_t* keys, int64_t n, uint32_t require,
+                         uint32_t bits, int64_t* hit /* nullable */);
+/* dr_host_tier_shrink with the dropped keys written to keys_out, in any    */
+/* order.  capacity < dr_host_tier_size is DR_INVALID_ARGUMENT before       */
+/* anything changes (no version is stamped).                                */
+int dr_host_tier_shrink_keys(dr_host_tier* t, int64_t global_step, int64_t steps_to_live,
+                             int64_t* keys_out, int64_t capacity,
+                             int64_t* removed /* nullable */);
 
 /* Per-key freq / version of the primary, host-side, syncs (tests/debug).   */
 int dr_ev_key_meta(dr_ev* ev, const int64_t* keys_host, int64_t n, int64_t* freq_host,
