@@ -70,6 +70,11 @@ struct EvShared {
   uint32_t* dirty = nullptr;
   float* pools[kMaxCols] = {nullptr};
   float* defaults[kMaxCols] = {nullptr};
+  // init table (dr_ev_set_init_table): the first touch of column c for key k
+  // copies row floor_mod(k, init_rows[c]) of the [init_rows[c], col_words]
+  // table; nullptr: every first touch copies defaults[c]
+  float* init_tab[kMaxCols] = {nullptr};
+  int32_t init_rows[kMaxCols] = {0};
   void* bloom = nullptr;
   uint64_t* seeds = nullptr;
   // host-side capacity accounting (no sync on the steady-state path)
@@ -497,12 +502,24 @@ __global__ void ev_bloom_add_kernel(EvGroup g, int T, const int64_t* __restrict_
   if (badd[i] > 0) bloom_addfreq(g.e[t], key, badd[i]);
 }
 
+// Row of an init table of `rows` rows that key k starts from: k mod rows as
+// a floor mod on the signed key (Python's %), never a mask -- rows need not be
+// a power of two.
+__device__ __forceinline__ int64_t init_tab_row(uint64_t key, int32_t rows) {
+  const int64_t m = (int64_t)key % (int64_t)rows;
+  return m < 0 ? m + rows : m;
+}
+
 // Copy the first-touch rows: pool[col][row_i] = src(i), group of 64 lanes
-// per key, lane-strided floats.  src(i) = src_rows[li*dim] or src_default.
+// per key, lane-strided floats.  src(i) = src_rows[li*dim], else the init
+// table's row of key i, else src_default.
 struct InitGroup {
   float* pool[DR_MAX_GROUP];
   const float* src[DR_MAX_GROUP];      // per-key rows ([n,dim]) or nullptr
   const float* dflt[DR_MAX_GROUP];     // column default (dim)
+  const float* tab[DR_MAX_GROUP];      // init table ([trows,dim]) or nullptr
+  int32_t trows[DR_MAX_GROUP];
+  const int64_t* keys;                 // the resolve's keys (read when tab is set)
   int64_t koff[DR_MAX_GROUP + 1];
   const int64_t* n_dev[DR_MAX_GROUP];
   const int32_t* tags;
@@ -547,7 +564,11 @@ __global__ void ev_init_rows_kernel(InitGroup g, int T, int64_t dim,
     const int64_t ll = __shfl(li, src_lane, 64);
     const int64_t ii = __shfl(i, src_lane, 64);
     const int64_t row = rows[ii];
-    const float* src = g.src[tt] ? g.src[tt] + ll * dim : g.dflt[tt];
+    const float* src = g.dflt[tt];
+    if (g.src[tt])
+      src = g.src[tt] + ll * dim;
+    else if (g.tab[tt])
+      src = g.tab[tt] + init_tab_row((uint64_t)g.keys[ii], g.trows[tt]) * dim;
     float* dst = g.pool[tt] + row * dim;
     for (int64_t c = lane; c < dim; c += 64) dst[c] = src[c];
   }
@@ -675,6 +696,9 @@ struct ApplyCols {
   const float* dflt[3];
   int ncol;
   int cols[3];
+  // rows of the primary column's init table, which dflt[0] then points at
+  // (1: dflt[0] is the column's single default row, as for every slot column)
+  int32_t trows0;
 };
 
 enum {
@@ -801,6 +825,9 @@ struct ApplyTable {
   // ev_adam_powers_kernel advances them after the apply when N > 0
   const float* powers;
 };
+// apply_probe's initmask: bits 0-2 = the columns this lane claimed the first
+// touch of, bits 3.. = the init-table row of the primary column (0: none)
+static constexpr int kInitRowShift = 3;
 static constexpr int kApplyGroup = 16;  // keeps the kernel arguments < 4 KiB
 struct ApplyGroup {
   ApplyTable t[kApplyGroup];
@@ -848,6 +875,10 @@ __device__ __forceinline__ void apply_probe(const ApplyTable& at, int64_t i, int
             const uint64_t old = atomicOr((unsigned long long*)&s->rc, (unsigned long long)bits);
             for (int c = 0; c < cols.ncol; ++c)
               if (!(old & (1ull << (48 + cols.cols[c])))) initmask |= 1 << c;
+            // only a lane that creates the primary row pays the 64-bit modulo
+            // (the init-table row rides above the three column bits: rows <= 2^20)
+            if ((initmask & 1) && cols.trows0 > 1)
+              initmask |= (int)init_tab_row(key, cols.trows0) << kInitRowShift;
           }
         }
       }
@@ -985,8 +1016,12 @@ __global__ __launch_bounds__(256) void ev_apply_kernel(ApplyGroup ag, int64_t di
       zs[q] = ga & 1;
       gp[q] = ok ? reinterpret_cast<const V*>((uintptr_t)(ga & ~(uint64_t)1))
                  : (WB && OPT == OPT_SGD ? reinterpret_cast<const V*>(cols.dflt[0]) : dg);
-      wp[q] = (ok && !(im & 1)) ? reinterpret_cast<const WT*>(cols.pool[0] + rr[q] * (WB ? dim / 2 : dim))
-                                : d0;
+      // the row's own var row, or -- first touch / skipped -- row im >> kInitRowShift
+      // of dflt[0] (the init table's row of this key; row 0 of a single default
+      // row); both strides are dv elements of WT
+      const bool own = ok && !(im & 1);
+      wp[q] = (own ? reinterpret_cast<const WT*>(cols.pool[0]) : d0) +
+              (own ? rr[q] : (int64_t)(im >> kInitRowShift)) * dv;
       ap1[q] = (OPT != OPT_SGD && ok && !(im & 2))
                    ? reinterpret_cast<const V*>(cols.pool[1] + rr[q] * dim) : d1;
       ap2[q] = (C3 && ok && !(im & 4))
@@ -1093,6 +1128,7 @@ __global__ __launch_bounds__(256) void ev_apply_ftrl_kernel(ApplyGroup ag, int64
     const int k = k0 + sub;
     int64_t r = __shfl(row, k, 64);  // every lane active for the shuffles
     const int im = __shfl(initmask, k, 64);
+    const int64_t t0 = (im >> kInitRowShift) * dv;  // the row's offset in the init table (0: none)
     if (base + k >= ne) r = -1;
     float ss = 0.f;
     const uint64_t ga = r >= 0 ? apply_grad_addr(grad, gind, base + k, dim) : 0;
@@ -1100,7 +1136,7 @@ __global__ __launch_bounds__(256) void ev_apply_ftrl_kernel(ApplyGroup ag, int64
       V* wp = reinterpret_cast<V*>(cols.pool[0] + r * dim);
       V* ap = reinterpret_cast<V*>(cols.pool[1] + r * dim);
       V* lp = reinterpret_cast<V*>(cols.pool[2] + r * dim);
-      const V* d0 = reinterpret_cast<const V*>(cols.dflt[0]);
+      const V* d0 = reinterpret_cast<const V*>(cols.dflt[0]) + t0;
       const V* d1 = reinterpret_cast<const V*>(cols.dflt[1]);
       const V* d2 = reinterpret_cast<const V*>(cols.dflt[2]);
       for (int64_t c = lg; c < dv; c += G) {
@@ -1131,7 +1167,7 @@ __global__ __launch_bounds__(256) void ev_apply_ftrl_kernel(ApplyGroup ag, int64
     V* wp = reinterpret_cast<V*>(cols.pool[0] + r * dim);
     V* ap = reinterpret_cast<V*>(cols.pool[1] + r * dim);
     const V* lp = reinterpret_cast<const V*>(cols.pool[2] + r * dim);
-    const V* d0 = reinterpret_cast<const V*>(cols.dflt[0]);
+    const V* d0 = reinterpret_cast<const V*>(cols.dflt[0]) + t0;
     const V* d1 = reinterpret_cast<const V*>(cols.dflt[1]);
     for (int64_t c = lg; c < dv; c += G) {
       const V gv = apply_grad_load<V>(ga, c);
@@ -1351,6 +1387,7 @@ static void free_shared(EvShared* s) {
   for (int c = 0; c < kMaxCols; ++c) {
     (void)hipFree(s->pools[c]);
     (void)hipFree(s->defaults[c]);
+    (void)hipFree(s->init_tab[c]);
   }
   (void)hipFree(s->bloom);
   (void)hipFree(s->seeds);
@@ -1582,6 +1619,7 @@ static int resolve_grouped(dr_ev* const* evs, int T, const int64_t* keys, const 
   bool any_bloom = false;
   g.tags = tags;
   ig.tags = tags;
+  ig.keys = keys;
   for (int t = 0; t < T; ++t) {
     g.e[t] = make_desc(evs[t]);
     g.koff[t] = composite ? 0 : koff[t];
@@ -1589,6 +1627,8 @@ static int resolve_grouped(dr_ev* const* evs, int T, const int64_t* keys, const 
     ig.pool[t] = evs[t]->sh->pools[evs[t]->col];
     ig.src[t] = defaults ? defaults[t] : nullptr;
     ig.dflt[t] = evs[t]->sh->defaults[evs[t]->col];
+    ig.tab[t] = evs[t]->sh->init_tab[evs[t]->col];
+    ig.trows[t] = evs[t]->sh->init_rows[evs[t]->col];
     ig.koff[t] = g.koff[t];
     ig.n_dev[t] = g.n_dev[t];
     any_bloom |= g.e[t].k_hash > 0;
@@ -1702,6 +1742,10 @@ static int apply_grouped(int opt, dr_ev* const* vars, dr_ev* const* s1, dr_ev* c
         a.cols.cols[c] = cv[c]->col;
         a.cols.pool[c] = s->pools[cv[c]->col];
         a.cols.dflt[c] = s->defaults[cv[c]->col];
+        if (c == 0) {  // the primary column's first touch: the key's init-table row
+          a.cols.trows0 = s->init_tab[0] ? s->init_rows[0] : 1;
+          if (s->init_tab[0]) a.cols.dflt[0] = s->init_tab[0];
+        }
         aligned = aligned && ((((uintptr_t)a.cols.pool[c]) | ((uintptr_t)a.cols.dflt[c])) & 15) == 0;
       }
       // by-address rows (gind) are 16-byte aligned when dim % 4 == 0
@@ -2170,6 +2214,8 @@ struct MissArgs {
   EvDesc e[DR_MAX_GROUP];
   float* pool[DR_MAX_GROUP];
   const float* dflt[DR_MAX_GROUP];
+  const float* tab[DR_MAX_GROUP];  // init table ([trows, dim]) or nullptr
+  int32_t trows[DR_MAX_GROUP];
   int64_t* mtop[DR_MAX_GROUP];  // row counters to mirror (nullptr: none)
   int64_t* mdst[DR_MAX_GROUP];
   const int64_t* keys;
@@ -2253,9 +2299,15 @@ __global__ __launch_bounds__(256) void ev_miss_kernel(MissArgs a, int T, int64_t
   const int64_t w0 = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
   for (int64_t i = w0; i < n; i += waves) {
     if (!minit[i]) continue;
-    const int t = (int)(mlist[i] % T);
+    int64_t b;
+    int t;
+    slot_bt(mlist[i], T, B, 0, &b, &t);
+    const float* src = a.dflt[t];
+    if (a.tab[t])
+      src = a.tab[t] +
+            init_tab_row((uint64_t)a.keys[b * a.ksb + (int64_t)t * a.kst], a.trows[t]) * dim;
     float* dst = a.pool[t] + mrow[i] * dim;
-    for (int64_t c = lane; c < dim; c += 64) dst[c] = a.dflt[t][c];
+    for (int64_t c = lane; c < dim; c += 64) dst[c] = src[c];
   }
   miss_grid_sync(bar, 2 * gridDim.x, st);
   for (int64_t i = w0; i < n; i += waves) {
@@ -2418,6 +2470,8 @@ static int lookup_onehot(dr_ev* const* evs, int T, const int64_t* keys, int64_t 
     ma.e[t] = make_desc(evs[t]);
     ma.pool[t] = s->pools[evs[t]->col];
     ma.dflt[t] = s->defaults[evs[t]->col];
+    ma.tab[t] = s->init_tab[evs[t]->col];
+    ma.trows[t] = s->init_rows[evs[t]->col];
   }
   la.io = make_lk_io(keys, ksb, kst, out, out_stride, rows_out, flags);
   ma.keys = keys;
@@ -3118,6 +3172,60 @@ int dr_ev_gather_tagged(dr_ev* const* evs, int num_tables, const int32_t* tags,
 
 const float* dr_ev_default_row(dr_ev* ev) {
   return ev ? ev->sh->defaults[ev->col] : nullptr;
+}
+
+// The initial row of a key becomes a function of the key alone, so the table
+// is fixed before the key space hands out its first row and never afterwards.
+int dr_ev_set_init_table(dr_ev* ev, const void* table_host, int64_t rows, void* stream) {
+  dr::EvGuard guard_(ev);
+  using namespace dr;
+  DR_REQUIRE(ev && table_host, DR_INVALID_ARGUMENT, "null argument");
+  DR_REQUIRE(rows >= 1 && rows <= DR_MAX_INIT_TABLE_ROWS, DR_INVALID_ARGUMENT,
+             "init table rows must be in [1, %lld] (got %lld)",
+             (long long)DR_MAX_INIT_TABLE_ROWS, (long long)rows);
+  EvShared* s = ev->sh;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(S(stream), &cs);
+  DR_REQUIRE(cs == hipStreamCaptureStatusNone, DR_INVALID_ARGUMENT,
+             "dr_ev_set_init_table inside stream capture");
+  // every insert any stream enqueued has run before the row counter is read
+  DR_HIP(hipDeviceSynchronize());
+  int64_t top = 0;
+  DR_HIP(hipMemcpy(&top, s->top, sizeof(int64_t), hipMemcpyDeviceToHost));
+  DR_REQUIRE(top == 0, DR_INVALID_ARGUMENT,
+             "dr_ev_set_init_table: the key space has handed out %lld rows (set the table "
+             "before the first key)", (long long)top);
+  const int64_t w = col_words(s, ev->col);
+  const size_t bytes = (size_t)rows * (size_t)w * sizeof(float);
+  float* tab = nullptr;
+  DR_HIP(hipMalloc(&tab, bytes));
+  hipError_t e;
+  if (w != s->dim) {
+    // bf16 column: the fp32 table rounded to nearest even, like the default row
+    const float* src = static_cast<const float*>(table_host);
+    std::vector<uint16_t> b((size_t)rows * (size_t)s->dim);
+    for (size_t c = 0; c < b.size(); ++c) b[c] = bf16_rne_host(src[c]);
+    e = hipMemcpy(tab, b.data(), bytes, hipMemcpyHostToDevice);
+  } else {
+    e = hipMemcpy(tab, table_host, bytes, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(tab);
+    set_error("dr_ev_set_init_table: copy failed: %s", hipGetErrorString(e));
+    return DR_INTERNAL;
+  }
+  (void)hipFree(s->init_tab[ev->col]);
+  s->init_tab[ev->col] = tab;
+  s->init_rows[ev->col] = (int32_t)rows;
+  return DR_OK;
+}
+
+int64_t dr_ev_init_table_rows(dr_ev* ev) {
+  return ev && ev->sh->init_tab[ev->col] ? ev->sh->init_rows[ev->col] : 1;
+}
+
+const float* dr_ev_init_table(dr_ev* ev) {
+  return ev ? ev->sh->init_tab[ev->col] : nullptr;
 }
 
 int dr_ev_gather(dr_ev* ev, const int64_t* keys, int64_t n, const float* defaults,
@@ -5803,10 +5911,18 @@ struct XgmiRowArgs {
   int64_t* mdst[DR_MAX_GROUP];   // their pinned host mirrors
 };
 
+// Init tables of the served EVs and the inbox keys the resolve just read
+// (an argument of the init kernel alone: the emit's XgmiRowArgs stay as they are).
+struct XgmiInitTabs {
+  const float* tab[DR_MAX_GROUP];  // init table ([trows, dim]) or nullptr
+  int32_t trows[DR_MAX_GROUP];
+  const int64_t* keys;             // local inbox [world][cap]
+};
+
 // Wave-cooperative first-touch copy (steady state: one byte per key); block
 // (0, 0) also mirrors the tables' row counters to the host (the resolve
 // before it has finished: the counters are final) -- no per-table copy launch.
-__global__ __launch_bounds__(256) void xgmi_init_kernel(XgmiRowArgs a,
+__global__ __launch_bounds__(256) void xgmi_init_kernel(XgmiRowArgs a, XgmiInitTabs it,
                                                         const int64_t* __restrict__ rows,
                                                         const uint8_t* __restrict__ init) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < a.T && a.mdst[threadIdx.x]) {
@@ -5831,6 +5947,7 @@ __global__ __launch_bounds__(256) void xgmi_init_kernel(XgmiRowArgs a,
       const int t = a.slot[jj] % a.T;
       float* dst = a.pool[t] + rows[jj] * a.dim;
       const float* src_row = a.dflt[t];
+      if (it.tab[t]) src_row = it.tab[t] + init_tab_row((uint64_t)it.keys[jj], it.trows[t]) * a.dim;
       for (int64_t c = lane; c < a.dim; c += 64) dst[c] = src_row[c];
     }
   }
@@ -6006,6 +6123,8 @@ int dr_xgmi_serve(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
   memset(&ra, 0, sizeof(ra));
   XgmiRowArgs wa;
   memset(&wa, 0, sizeof(wa));
+  XgmiInitTabs it;
+  memset(&it, 0, sizeof(it));
   for (int t = 0; t < num_tables; ++t) {
     const EvShared* s = evs[t]->sh;
     DR_REQUIRE(col_words(s, evs[t]->col) == dim && s->bf16 == evs[0]->sh->bf16,
@@ -6019,6 +6138,7 @@ int dr_xgmi_serve(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
   DR_REQUIRE(peers->inbox_keys[r] && peers->inbox_slot[r] && peers->inbox_cnt[r],
              DR_INVALID_ARGUMENT, "own inbox not set");
   ra.keys = peers->inbox_keys[r];
+  it.keys = ra.keys;
   ra.slot = peers->inbox_slot[r];
   ra.cnt = peers->inbox_cnt[r];
   ra.cap = peers->cap;
@@ -6047,6 +6167,8 @@ int dr_xgmi_serve(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
     ra.e[t] = make_desc(evs[t]);   // grow() may have moved the table / pools
     wa.pool[t] = evs[t]->sh->pools[evs[t]->col];
     wa.dflt[t] = evs[t]->sh->defaults[evs[t]->col];
+    it.tab[t] = evs[t]->sh->init_tab[evs[t]->col];
+    it.trows[t] = evs[t]->sh->init_rows[evs[t]->col];
   }
   // One-shot grids sized for 1.25x the keys a source sends on average
   // (T*B / W for keys spread over owners); the kernels' grid-stride loops
@@ -6073,7 +6195,8 @@ int dr_xgmi_serve(const dr_xgmi_peers* peers, dr_ev* const* evs, int num_tables,
       sh->mu.unlock();
     }
   }
-  hipLaunchKernelGGL(xgmi_init_kernel, dim3(gx, W), dim3(256), 0, st, wa, w.rows, w.init);
+  hipLaunchKernelGGL(xgmi_init_kernel, dim3(gx, W), dim3(256), 0, st, wa, it, w.rows,
+                     w.init);
   {
     const hipError_t le = hipGetLastError();
     for (int q = 0; q < nmir; ++q) {

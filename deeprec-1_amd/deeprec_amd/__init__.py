@@ -14,8 +14,8 @@ from .embedding_ops import (DenseTable, SparseTensor, embedding_lookup, embeddin
                             embedding_lookup_sparse_multi, fused_embedding_lookup_sparse,
                             safe_embedding_lookup_sparse)
 from .kv_variable_ops import (CBFFilter, CounterFilter, EmbeddingVariable, EmbeddingVariableOption,
-                              GlobalStepEvict, IndexedSlices, KeyBudgetEvict, StorageOption,
-                              StorageType, flush_releases, get_embedding_variable,
+                              GlobalStepEvict, IndexedSlices, InitializerOption, KeyBudgetEvict,
+                              StorageOption, StorageType, flush_releases, get_embedding_variable,
                               read_only_lookups)
 from .ops import set_validate, status_check
 from .string_ops import StringTensor, string_to_hash_bucket_fast
@@ -30,5 +30,5 @@ __all__ = [
     "IndexedSlices", "KeyBudgetEvict", "get_embedding_variable", "read_only_lookups", "set_validate", "status_check",
     "AdagradOptimizer", "AdagradDecayOptimizer", "AdamAsyncOptimizer", "AdamOptimizer",
     "FtrlOptimizer", "GradientDescentOptimizer", "StringTensor",
-    "string_to_hash_bucket_fast", "StorageOption", "StorageType",
+    "string_to_hash_bucket_fast", "StorageOption", "StorageType", "InitializerOption",
 ]

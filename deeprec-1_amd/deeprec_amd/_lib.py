@@ -219,6 +219,9 @@ SIGNATURES = {
     "dr_ev_gather_tagged": (_I32, [_P, _I32, _P, _P, _I64, _P, _P, _P]),
     "dr_ev_pool": (_P, [_P]),
     "dr_ev_default_row": (_P, [_P]),
+    "dr_ev_set_init_table": (_I32, [_P, _P, _I64, _P]),
+    "dr_ev_init_table_rows": (_I64, [_P]),
+    "dr_ev_init_table": (_P, [_P]),
     "dr_ev_gather_workspace_size": (_SZ, [_I64]),
     "dr_ev_gather": (_I32, [_P, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
     "dr_ev_find_grouped": (_I32, [_P, _I32, _P, _P, _P, _P, _P]),

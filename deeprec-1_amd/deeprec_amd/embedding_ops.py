@@ -65,6 +65,14 @@ _FUSED_ONEHOT = os.environ.get("DEEPREC_AMD_FUSED_ONEHOT", "1") != "0"
 _ROWS_GRAD = os.environ.get("DEEPREC_AMD_ROWS_GRAD", "1") != "0"
 
 
+def _draws_defaults(ev):
+    """The EV draws a fresh [N, D] default block with torch on every lookup
+    (a callable initializer without an init_option): it is prepared alone and
+    takes none of the grouped / fused / recorded-rows routes.  An EV with an
+    InitializerOption starts its keys from its init table on the device."""
+    return ev.draws_defaults_per_call()
+
+
 def _ev_default_dev(ev):
     d = getattr(ev, "_default_dev", None)
     if d is None:
@@ -400,7 +408,7 @@ def _prepare_all(feats, need_grad):
     for f in feats:
         p = f.params
         key = None
-        if isinstance(p, EmbeddingVariable) and not callable(p.initializer):
+        if isinstance(p, EmbeddingVariable) and not _draws_defaults(p):
             key = (p.dim, str(p.device), f.batch)
         sets.setdefault(key, []).append(f)
     for key, fs in sets.items():
@@ -416,7 +424,7 @@ def _prepare_all(feats, need_grad):
 def _groupable(feats):
     p0 = feats[0].params
     return (len(feats) > 1 and len(feats) <= _lib.MAX_GROUP
-            and all(isinstance(f.params, EmbeddingVariable) and not callable(f.params.initializer)
+            and all(isinstance(f.params, EmbeddingVariable) and not _draws_defaults(f.params)
                     and f.params.dim == p0.dim and f.params.device == p0.device for f in feats))
 
 
@@ -501,7 +509,7 @@ def _rows_eligible(feats):
         return False
     p0 = feats[0].params
     return all(isinstance(f.params, EmbeddingVariable) and f.params.filter_freq == 0
-               and not callable(f.params.initializer) and f.max_norm is None
+               and not _draws_defaults(f.params) and f.max_norm is None
                and f.params.dim == p0.dim and f.params.device == p0.device
                and f.batch == feats[0].batch for f in feats)
 
@@ -778,7 +786,7 @@ def _fused_onehot_ok(feats):
         p = f.params
         if not (isinstance(p, EmbeddingVariable) and f.onehot and f.batch == B
                 and p.dim == D and p.device == p0.device and p.filter_freq == 0
-                and not callable(p.initializer) and f.raw_values.numel() == B
+                and not _draws_defaults(p) and f.raw_values.numel() == B
                 and p.value_dtype == p0.value_dtype):
             return False
     W = p0.row_words

@@ -89,7 +89,34 @@ class StorageOption(object):
         self.incremental = bool(incremental)
 
 
+MAX_INIT_TABLE_ROWS = 1 << 20     # DR_MAX_INIT_TABLE_ROWS
+
+
+class InitializerOption(object):
+    """variables.py InitializerOption: the initializer is
+    run once, for a [default_value_dim, dim] table, and a new key k starts from
+    table row k % default_value_dim (EmbeddingVar::GetDefaultValue) -- a floor
+    mod, so the initial row is a function of the key alone.  A key the filter
+    has not admitted (and a read-only miss) reads a row of
+    default_value_no_permission.  initializer None: the EV's own initializer=
+    argument; a constant is broadcast."""
+
+    def __init__(self, initializer=None, default_value_dim=4096, default_value_no_permission=0.0):
+        k = int(default_value_dim)
+        if k < 1 or k > MAX_INIT_TABLE_ROWS:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "InitializerOption: default_value_dim must be in "
+                "[1, %d], not %d" % (MAX_INIT_TABLE_ROWS, k))
+        self.initializer = initializer
+        self.default_value_dim = k
+        self.default_value_no_permission = float(default_value_no_permission)
+
+
 class EmbeddingVariableOption(object):
+    # The constructor's parameter list is pinned (tests/test_host_tier_abi.py), so
+    # the InitializerOption is an attribute: set it, or chain with_init_option().
+    init_option = None
+
     def __init__(self, ht_type="", ht_partition_num=1000, evict_option=None, filter_option=None,
                  storage_option=None):
         self.ht_type = ht_type
@@ -97,6 +124,12 @@ class EmbeddingVariableOption(object):
         self.evict_option = evict_option
         self.filter_option = filter_option
         self.storage_option = storage_option
+
+    def with_init_option(self, init_option):
+        """Set the InitializerOption and return self:
+        EmbeddingVariableOption(...).with_init_option(InitializerOption(...))."""
+        self.init_option = init_option
+        return self
 
 
 def _default_row(initializer, dim, device, dtype=torch.float32):
@@ -108,6 +141,29 @@ def _default_row(initializer, dim, device, dtype=torch.float32):
         v = torch.as_tensor(v, dtype=dtype).reshape(dim)
     else:
         v = torch.full((dim,), float(initializer), dtype=dtype)
+    return v.cpu().contiguous()
+
+
+def _init_table_host(init_option, initializer, dim, dtype=torch.float32, name=""):
+    """The [default_value_dim, dim] host table of an InitializerOption: its
+    initializer (or else the EV's) called once with that shape; a constant is
+    broadcast."""
+    k = int(init_option.default_value_dim)
+    if k < 1 or k > MAX_INIT_TABLE_ROWS:       # (the attribute may have been reassigned)
+        raise _lib.InvalidArgumentError(
+            _lib.INVALID_ARGUMENT, "InitializerOption: default_value_dim must be in [1, %d], "
+            "not %d (%s)" % (MAX_INIT_TABLE_ROWS, k, name))
+    ini = init_option.initializer if init_option.initializer is not None else initializer
+    if ini is None:
+        ini = 0.0
+    if callable(ini):
+        v = torch.as_tensor(ini((k, dim)), dtype=dtype)
+        if tuple(v.shape) != (k, dim):
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "InitializerOption: the initializer returned shape %s "
+                "for (%d, %d) (%s)" % (tuple(v.shape), k, dim, name))
+    else:
+        v = torch.full((k, dim), float(ini), dtype=dtype)
     return v.cpu().contiguous()
 
 
@@ -332,6 +388,9 @@ class EmbeddingVariable(object):
     lambda s: torch.randn(s) * 0.01).  As in the reference, a callable
     initializer draws a fresh [N, D] default block per sparse_read call
     (kv_variable_ops.py:651-654); a constant uses the EV's own default row.
+    With EmbeddingVariableOption().with_init_option(InitializerOption(...)) the
+    initializer is called once instead, for the EV's init table on the device:
+    a new key k starts from init_table[k % default_value_dim] on every path.
     """
 
     def __init__(self, name, embedding_dim, initializer=None, steps_to_live=0, ev_option=None,
@@ -402,8 +461,19 @@ class EmbeddingVariable(object):
         bf16 = self.value_dtype == torch.bfloat16
         # the C ABI takes the default row in fp32 (a bf16 EV rounds it to
         # nearest even, as the .to(torch.bfloat16) below does)
-        default = _default_row(initializer, self.dim, self.device,
-                               torch.float32 if bf16 else self.value_dtype)
+        host_dtype = torch.float32 if bf16 else self.value_dtype
+        # InitializerOption (primary EVs; slots keep their single default row):
+        # the table is drawn once, here, and the default row -- what a lookup
+        # serves when it serves no stored row -- is default_value_no_permission
+        io = opt.init_option if _primary is None else None
+        self._init_table_host = None
+        self._init_table_dev = None
+        if io is not None:
+            self._init_table_host = _init_table_host(io, initializer, self.dim, host_dtype, name)
+            default = _default_row(io.default_value_no_permission, self.dim, self.device,
+                                   host_dtype)
+        else:
+            default = _default_row(initializer, self.dim, self.device, host_dtype)
         self._default_host = default.to(torch.bfloat16) if bf16 else default
         h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -420,6 +490,13 @@ class EmbeddingVariable(object):
                 cfg.layout = 1 if (self.filter_freq or self.steps_to_live) else 0
                 cfg.value_bits = {torch.float64: 64, torch.bfloat16: 16}.get(self.value_dtype, 32)
                 check(lib().dr_ev_create(C.byref(cfg), default.data_ptr(), C.byref(h)))
+                if self._init_table_host is not None:
+                    rc = lib().dr_ev_set_init_table(h, self._init_table_host.data_ptr(),
+                                                    self._init_table_host.shape[0],
+                                                    stream_handle(self.device))
+                    if rc:
+                        _release_handle(h)
+                        check(rc)
             else:
                 check(lib().dr_ev_create_slot(_primary._h, _slot_index, default.data_ptr(),
                                               C.byref(h)))
@@ -474,6 +551,21 @@ class EmbeddingVariable(object):
     def default_value(self):
         return self._default_host.to(self.device)
 
+    @property
+    def init_table(self):
+        """The [default_value_dim, dim] init table in the value dtype (device),
+        as the kernels read it; None without an init_option."""
+        if self._init_table_host is None:
+            return None
+        if self._init_table_dev is None:
+            self._init_table_dev = self._init_table_host.to(self.value_dtype).to(self.device)
+        return self._init_table_dev
+
+    def draws_defaults_per_call(self):
+        """A callable initializer without an init_option: every lookup draws a
+        fresh [N, D] default block with torch (_defaults_for)."""
+        return callable(self.initializer) and self._init_table_host is None
+
     def pool(self):
         """Base pointer of this EV's value rows (device)."""
         return lib().dr_ev_pool(self._h)
@@ -493,7 +585,7 @@ class EmbeddingVariable(object):
         if ev_init_value is not None:
             return torch.as_tensor(ev_init_value, dtype=self.value_dtype,
                                    device=self.device).expand(n, self.dim).contiguous()
-        if callable(self.initializer):
+        if self.draws_defaults_per_call():
             v = self.initializer((n, self.dim))
             return torch.as_tensor(v, dtype=self.value_dtype, device=self.device).reshape(
                 n, self.dim).contiguous()

@@ -522,6 +522,29 @@ const float* dr_ev_pool(dr_ev* ev);
 /* Device pointer of this EV's default row (dim floats).                    */
 const float* dr_ev_default_row(dr_ev* ev);
 
+/* Init table (DeepRec's InitializerOption: default_value_dim rows drawn     */
+/* once).  Column ev->col of the key space gets a device copy of the HOST    */
+/* table [rows, dim], in the element type and rounding of that EV's          */
+/* default_row_host (float / double as is; fp32 rounded to nearest even for  */
+/* a bf16 primary); it is freed with the key space.  From then on the first  */
+/* touch of that column for key k -- by a resolve / gather, a one-hot        */
+/* lookup's miss path, an apply that names a key no lookup created, or the   */
+/* XGMI owner side -- copies table row m = k % rows; if (m < 0) m += rows    */
+/* (a floor mod on the signed key; -1 and INT64_MIN are ordinary keys).  An  */
+/* explicit `defaults` argument still wins.  The single default row keeps    */
+/* its other role: it is what a lookup serves when it serves no stored row   */
+/* (a key the filter has not admitted, a read-only miss, pool exhaustion).   */
+/* rows in [1, DR_MAX_INIT_TABLE_ROWS].  DR_INVALID_ARGUMENT: a null EV or   */
+/* table, rows out of range, inside stream capture, or once the key space    */
+/* has handed out a row (a table changed later would break "initial row =    */
+/* f(key)"); the table then stays as it was.  Synchronises the device.       */
+#define DR_MAX_INIT_TABLE_ROWS (1 << 20)
+int dr_ev_set_init_table(dr_ev* ev, const void* table_host, int64_t rows, void* stream);
+/* Rows of this column's init table; 1 when none is set.                     */
+int64_t dr_ev_init_table_rows(dr_ev* ev);
+/* Device pointer of this column's init table, or NULL.                      */
+const float* dr_ev_init_table(dr_ev* ev);
+
 /* KvResourceGather (counts == NULL) / KvResourceGatherV1.                   */
 size_t dr_ev_gather_workspace_size(int64_t n);
 int dr_ev_gather(dr_ev* ev, const int64_t* keys, int64_t n, const float* defaults,
