@@ -6288,3 +6288,169 @@ int dr_xgmi_serve_readonly(const dr_xgmi_peers* peers, dr_ev* const* evs, int nu
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// Serving pooled read-only lookups from the host-DRAM tier in place (DESIGN
+// section 19).  The host fetched the rows the tier serves for this batch and
+// uploaded them as an overlay: ov_keys[M] (strictly ascending as signed int64
+// inside each table's range ov_off[t] .. ov_off[t + 1]) and ov_rows[M, words].
+// Neither kernel touches a table: both read the overlay alone.
+//   resolve : after dr_ev_find_grouped.  Lane per key; a row >= 0 stays, a
+//             negative one becomes -(2 + j) for the key at global overlay
+//             index j, else -1 -- the codes the pooling kernels turn into
+//             default_rows + (-r - 1) * default_stride.
+//   patch   : after dr_ev_lookup_onehot_readonly, which wrote the default at
+//             every position whose key HBM does not hold.  16 lanes per entry
+//             of dr_ev_missing_keys' list; a key the overlay holds has its
+//             row written over the default through the fused kernel's own
+//             load / store helpers (load_row_copy_u, store_row_sel).
+// ===========================================================================
+#include "dr_overlay.h"
+
+namespace dr {
+
+struct OvGroup {
+  int64_t koff[DR_MAX_GROUP + 1];
+  int64_t ooff[DR_MAX_GROUP + 1];
+  const int64_t* n_dev[DR_MAX_GROUP];
+};
+static_assert(sizeof(OvGroup) + 64 <= 4096, "overlay kernel arguments exceed 4 KiB");
+
+__global__ __launch_bounds__(256) void ev_overlay_resolve_kernel(
+    OvGroup g, int T, const int64_t* __restrict__ keys, const int64_t* __restrict__ ov_keys,
+    int64_t* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.koff[T]) return;
+  const int t = table_of(g.koff, T, i, (int64_t)blockIdx.x * blockDim.x);
+  const int64_t li = i - g.koff[t];
+  if (g.n_dev[t] && li >= *g.n_dev[t]) return;
+  if (rows[i] >= 0) return;
+  const int64_t j = overlay_find(ov_keys, g.ooff[t], g.ooff[t + 1], keys[i]);
+  rows[i] = j >= 0 ? -(2 + j) : -1;
+}
+
+// `dim`: float words of one table's columns in an output row; `words`: float
+// words of an overlay row (WIDEN: bf16 rows into an fp32 output, dim = 2 words).
+template <int ORDER, bool WIDEN>
+__global__ __launch_bounds__(256) void ev_overlay_patch_kernel(
+    OvGroup g, int T, const int64_t* __restrict__ miss_keys, const int64_t* __restrict__ miss_pos,
+    int64_t m, const int64_t* __restrict__ ov_keys, const float* __restrict__ ov_rows,
+    int64_t words, float* __restrict__ out, int64_t out_stride, int dim) {
+  constexpr int G = 16;
+  const int64_t i = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  if (i >= m) return;
+  const int64_t p = miss_pos[i];
+  if (p < 0 || p >= g.koff[T]) return;
+  const int t = table_of(g.koff, T, p, p);
+  const int64_t b = p - g.koff[t];
+  const int64_t j = overlay_find(ov_keys, g.ooff[t], g.ooff[t + 1], miss_keys[i]);
+  if (j < 0) return;
+  const float* src = ov_rows + j * words;
+  float* dst = out + b * out_stride + (int64_t)t * dim;
+  const int dv = dim / 4;
+  for (int c = threadIdx.x % G; c < dv; c += G) {
+    Row<4, G, 1> x;
+    load_row_copy_u<4, G, WIDEN>(x, src, c, dv);
+    store_row_sel<4, G, ORDER>(x, dst, dst, c, dv);  // (c < dv: the junk line is never chosen)
+  }
+}
+
+static int overlay_group(OvGroup* g, int T, const int64_t* koff, const int64_t* ooff,
+                         const int64_t* const* n_dev) {
+  DR_REQUIRE(T >= 1 && T <= DR_MAX_GROUP, DR_INVALID_ARGUMENT, "bad table count %d", T);
+  memset(g, 0, sizeof(*g));
+  DR_REQUIRE(koff[0] >= 0 && ooff[0] >= 0, DR_INVALID_ARGUMENT, "offsets must start at >= 0");
+  for (int t = 0; t < T; ++t) {
+    DR_REQUIRE(koff[t + 1] >= koff[t] && ooff[t + 1] >= ooff[t], DR_INVALID_ARGUMENT,
+               "koff / ov_off must be non-decreasing");
+    g->n_dev[t] = n_dev ? n_dev[t] : nullptr;
+  }
+  for (int t = 0; t <= T; ++t) {
+    g->koff[t] = koff[t];
+    g->ooff[t] = ooff[t];
+  }
+  return DR_OK;
+}
+
+}  // namespace dr
+
+extern "C" {
+
+int dr_ev_overlay_resolve(const int64_t* keys, const int64_t* koff_host,
+                          const int64_t* const* n_dev_per_table, int num_tables,
+                          const int64_t* ov_keys, const int64_t* ov_off_host, int64_t* rows_inout,
+                          void* stream) {
+  using namespace dr;
+  DR_REQUIRE(keys && koff_host && ov_keys && ov_off_host && rows_inout, DR_INVALID_ARGUMENT,
+             "dr_ev_overlay_resolve: null argument");
+  OvGroup g;
+  const int rc = overlay_group(&g, num_tables, koff_host, ov_off_host, n_dev_per_table);
+  if (rc) return rc;
+  const int64_t total = g.koff[num_tables];
+  if (total == 0) return DR_OK;
+  hipLaunchKernelGGL(ev_overlay_resolve_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0,
+                     S(stream), g, num_tables, keys, ov_keys, rows_inout);
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+int dr_ev_overlay_patch_onehot(const int64_t* miss_keys, const int64_t* miss_pos, int64_t m,
+                               const int64_t* koff_host, int num_tables, const int64_t* ov_keys,
+                               const int64_t* ov_off_host, const void* ov_rows, int64_t row_words,
+                               void* out, int64_t out_stride, int64_t dim, int order, int flags,
+                               void* stream) {
+  using namespace dr;
+  DR_REQUIRE(miss_keys && miss_pos && koff_host && ov_keys && ov_off_host && ov_rows && out,
+             DR_INVALID_ARGUMENT, "dr_ev_overlay_patch_onehot: null argument");
+  DR_REQUIRE(m >= 0 && row_words > 0 && dim > 0 && out_stride >= 0, DR_INVALID_ARGUMENT,
+             "bad argument");
+  DR_REQUIRE(order == DR_ORDER_ALI || order == DR_ORDER_SEQ, DR_INVALID_ARGUMENT, "bad order");
+  DR_REQUIRE((flags & ~(DR_LOOKUP_OUT_BF16 | DR_LOOKUP_TABLE_ORDER)) == 0, DR_INVALID_ARGUMENT,
+             "unknown flags 0x%x", flags);
+  OvGroup g;
+  const int T = num_tables;
+  const int rc = overlay_group(&g, T, koff_host, ov_off_host, nullptr);
+  if (rc) return rc;
+  const int64_t B = g.koff[1] - g.koff[0];
+  for (int t = 0; t < T; ++t)
+    DR_REQUIRE(g.koff[t + 1] - g.koff[t] == B, DR_INVALID_ARGUMENT,
+               "one-hot lookup: every table has the batch's number of ids");
+  // the three cases of lookup_check: fp32 rows, bf16 rows widened, bf16 rows copied
+  const bool bf16 = row_words * 2 == dim;
+  const bool out_bf16 = flags & DR_LOOKUP_OUT_BF16;
+  DR_REQUIRE(bf16 || row_words == dim, DR_INVALID_ARGUMENT,
+             "row_words %lld for dim %lld: fp32 rows hold dim words, bf16 rows dim / 2",
+             (long long)row_words, (long long)dim);
+  DR_REQUIRE(!out_bf16 || bf16, DR_INVALID_ARGUMENT, "DR_LOOKUP_OUT_BF16 needs bf16 rows");
+  DR_REQUIRE(!bf16 || order == DR_ORDER_ALI, DR_INVALID_ARGUMENT,
+             "bf16 EV lookups pool in the ALI order");
+  DR_REQUIRE(!out_bf16 || out_stride % 2 == 0, DR_INVALID_ARGUMENT,
+             "bf16 output stride must be even");
+  const bool widen = bf16 && !out_bf16;
+  if (out_bf16) out_stride /= 2;
+  const int64_t wd = out_bf16 ? row_words : dim;  // float words per table in an output row
+  DR_REQUIRE(row_words % 4 == 0 && row_words <= 256 && wd % 4 == 0, DR_INVALID_ARGUMENT,
+             "fused one-hot lookup needs row words %% 4 == 0 and <= 256");
+  DR_REQUIRE(out_stride >= (int64_t)T * wd && out_stride % 4 == 0 &&
+                 (((uintptr_t)out | (uintptr_t)ov_rows) & 15) == 0,
+             DR_INVALID_ARGUMENT,
+             "out and ov_rows must be 16-B aligned, out stride >= T*dim (multiple of 4)");
+  if (m == 0 || g.ooff[T] == 0) return DR_OK;
+  const dim3 grid((unsigned)ceil_div(m, 16));
+  float* o = static_cast<float*>(out);
+  const float* r = static_cast<const float*>(ov_rows);
+#define DR_OV_PATCH(ORDER, WIDEN)                                                              \
+  hipLaunchKernelGGL((ev_overlay_patch_kernel<ORDER, WIDEN>), grid, dim3(256), 0, S(stream), g, \
+                     T, miss_keys, miss_pos, m, ov_keys, r, row_words, o, out_stride, (int)wd)
+  if (widen)
+    DR_OV_PATCH(DR_ORDER_ALI, true);
+  else if (order == DR_ORDER_ALI)
+    DR_OV_PATCH(DR_ORDER_ALI, false);
+  else
+    DR_OV_PATCH(DR_ORDER_SEQ, false);
+#undef DR_OV_PATCH
+  DR_LAUNCH_CHECK();
+  return DR_OK;
+}
+
+}  // extern "C"

@@ -16,7 +16,7 @@ from .embedding_ops import (DenseTable, SparseTensor, embedding_lookup, embeddin
 from .kv_variable_ops import (CBFFilter, CounterFilter, EmbeddingVariable, EmbeddingVariableOption,
                               GlobalStepEvict, IndexedSlices, InitializerOption, KeyBudgetEvict,
                               StorageOption, StorageType, flush_releases, get_embedding_variable,
-                              read_only_lookups)
+                              read_only_lookups, read_only_serves_tier)
 from .ops import set_validate, status_check
 from .string_ops import StringTensor, string_to_hash_bucket_fast
 from .training import (AdagradDecayOptimizer, AdagradOptimizer, AdamAsyncOptimizer, AdamOptimizer,
@@ -31,4 +31,5 @@ __all__ = [
     "AdagradOptimizer", "AdagradDecayOptimizer", "AdamAsyncOptimizer", "AdamOptimizer",
     "FtrlOptimizer", "GradientDescentOptimizer", "StringTensor",
     "string_to_hash_bucket_fast", "StorageOption", "StorageType", "InitializerOption",
+    "read_only_serves_tier",
 ]

@@ -268,6 +268,9 @@ SIGNATURES = {
     "dr_host_tier_clear_bits": (_I32, [_P, C.c_uint32, _P]),
     "dr_host_tier_or_bits": (_I32, [_P, _P, _I64, C.c_uint32, C.c_uint32, _P]),
     "dr_host_tier_shrink_keys": (_I32, [_P, _I64, _I64, _P, _I64, _P]),
+    "dr_ev_overlay_resolve": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P]),
+    "dr_ev_overlay_patch_onehot": (_I32, [_P, _P, _I64, _P, _I32, _P, _P, _P, _I64, _P, _I64, _I64,
+                                          _I32, _I32, _P]),
     "dr_ev_key_meta": (_I32, [_P, _P, _I64, _P, _P, _P, _P]),
     "dr_ev_apply_sgd": (_I32, [_P, _F32, _P, _P, _I64, _P, _I64, _P]),
     "dr_ev_apply_adagrad": (_I32, [_P, _P, _F32, _P, _P, _I64, _P, _I64, _P]),

@@ -18,7 +18,8 @@ import torch
 from . import _lib, ops
 from ._lib import COMBINERS, ORDER_ALI, ORDER_SEQ, DrPoolDesc, check, lib, ptr, stream_handle, workspace
 from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
-                               promote_grouped, read_only_active, tier_hits)
+                               _refuse_tier_capture, promote_grouped, read_only_active,
+                               read_only_serves_tier, tier_hits, tier_serve_overlay)
 
 
 class SparseTensor(object):
@@ -126,6 +127,8 @@ class _Feature(object):
         self.max_norm = max_norm
         self.uniq = self.idx = self.U = self.rows = self.rowsel = None
         self.defaults = None
+        # [default row ; the rows the host tier serves for this lookup] (_prepare_readonly)
+        self.overlay_rows = None
 
     @property
     def values(self):
@@ -219,8 +222,13 @@ def _desc(f, out, out_stride):
         d.pool = p.pool()
         d.pool_rows = 1 << 62
         d.ids = ptr(f.rowsel)                      # pre-resolved row per nnz
-        d.default_rows = ptr(_ev_default_dev(p))
-        d.default_stride = 0
+        if f.overlay_rows is not None:
+            # rowsel -1: row 0, the default; -(2 + j): row 1 + j, served by the host tier
+            d.default_rows = ptr(f.overlay_rows)
+            d.default_stride = p.dim
+        else:
+            d.default_rows = ptr(_ev_default_dev(p))
+            d.default_stride = 0
     elif isinstance(p, EmbeddingVariable):
         d.pool = p.pool()
         d.pool_rows = 0
@@ -879,11 +887,13 @@ def _fused_onehot(feats, order, with_rows=False, out_dtype=None):
     return out
 
 
-def _fused_onehot_readonly(feats, order, out_dtype=None):
+def _fused_onehot_readonly(feats, order, out_dtype=None, serve_tier=False):
     """One-hot read-only lookup in one launch (dr_ev_lookup_onehot_readonly:
     probe + row copy, absent ids read the default row).  Filter EVs and EVs
     with a callable initializer qualify: nothing is created, so neither the
-    filter nor the initializer runs.  None when the features do not qualify."""
+    filter nor the initializer runs.  None when the features do not qualify.
+    serve_tier: the ids the host tier serves then have their row written over
+    the default (dr_ev_overlay_patch_onehot)."""
     import ctypes as C
     p0 = feats[0].params
     B = feats[0].batch
@@ -900,26 +910,40 @@ def _fused_onehot_readonly(feats, order, out_dtype=None):
     dev = feats[0].raw_values.device
     odt = _out_dtype(feats, out_dtype)
     flags = _lib.LOOKUP_OUT_BF16 if odt == torch.bfloat16 else 0
+    koff = [t * B for t in range(T + 1)]
+    ov = vals = None
+    if serve_tier and _tiered_feats(feats):
+        vals = _concat_values(feats, koff)
+        ov = tier_serve_overlay([f.params for f in feats], vals, koff=koff)
     out = torch.empty((B, T * D), dtype=odt, device=dev)
     handles = (C.c_void_p * T)(*[f.params.handle.value for f in feats])
     rec = _record_major(feats)
     if rec is not None:
         keys, ksb, kst = rec, T, 1
     else:
-        vals = _concat_values(feats, [t * B for t in range(T + 1)])
+        if vals is None:
+            vals = _concat_values(feats, koff)
         keys, ksb, kst = ptr(vals), 1, B
         if _TABLE_ORDER:
             flags |= _lib.LOOKUP_TABLE_ORDER
     check(lib().dr_ev_lookup_onehot_readonly(handles, T, keys, ksb, kst, B, ptr(out), T * D, order,
                                              flags, None, stream_handle(dev)))
+    if ov is not None:
+        check(lib().dr_ev_overlay_patch_onehot(
+            ptr(ov.miss_keys), ptr(ov.miss_pos), ov.miss_keys.numel(), ops._koff_array(koff), T,
+            ptr(ov.keys), ov.off_array(), ptr(ov.blob), W, ptr(out), T * D, D, order,
+            flags & _lib.LOOKUP_OUT_BF16, stream_handle(dev)))
     ops._post(dev)
     return out
 
 
-def _prepare_readonly(feats):
+def _prepare_readonly(feats, serve_tier=False):
     """Unique -> dr_ev_find_grouped -> row per nnz, for <= MAX_GROUP EV
     features: the row-per-nnz form the pooling kernels take (_desc), with the
-    EV default row for every id that is not served."""
+    EV default row for every id that is not served.  serve_tier: the unique
+    ids HBM does not hold are looked up in the host tier (tier_serve_overlay),
+    and the ones it serves resolve to a row of the feature's overlay block
+    (dr_ev_overlay_resolve)."""
     import ctypes as C
     dev = feats[0].values.device
     T = len(feats)
@@ -932,14 +956,30 @@ def _prepare_readonly(feats):
     rowsel = torch.empty(max(koff[-1], 1), dtype=torch.int64, device=dev)
     handles = (C.c_void_p * T)(*[f.params.handle.value for f in feats])
     ndev = (C.c_void_p * T)(*[U.data_ptr() + 8 * t for t in range(T)])
+    ov = None
+    if serve_tier and koff[-1] and _tiered_feats(feats):
+        ov = tier_serve_overlay([f.params for f in feats], uniq,
+                                [U[t:t + 1] for t in range(T)], koff=koff)
     check(lib().dr_ev_find_grouped(handles, T, ptr(uniq), ops._koff_array(koff), ndev, ptr(rows),
                                    stream_handle(dev)))
+    if ov is not None:
+        check(lib().dr_ev_overlay_resolve(ptr(uniq), ops._koff_array(koff), ndev, T, ptr(ov.keys),
+                                          ov.off_array(), ptr(rows), stream_handle(dev)))
     check(lib().dr_rows_per_nnz(ptr(rows), ptr(idx), ops._koff_array(koff), T, ptr(rowsel),
                                 stream_handle(dev)))
     ops._post(dev)
     for t, f in enumerate(feats):
         f.uniq = f.idx = f.rows = f.U = f.defaults = f.group = None
         f.rowsel = rowsel[koff[t]:koff[t + 1]]
+        f.overlay_rows = None
+        if ov is not None and ov.off[t + 1] > ov.off[t]:
+            p = f.params
+            f.overlay_rows = torch.cat([_ev_default_dev(p).view(1, p.dim),
+                                        ov.rows(t, p.value_dtype)])
+            if ov.off[t]:
+                # the codes carry the global overlay index: rebased to this table's block
+                rs = f.rowsel
+                rs.add_((rs < -1).to(torch.int64), alpha=ov.off[t])
 
 
 def _run_readonly(feats, order, out_dtype):
@@ -958,14 +998,18 @@ def _run_readonly(feats, order, out_dtype):
                 parts[id(f)] = res[:, col:col + d]
                 col += d
         return torch.cat([parts[id(f)] for f in feats], 1)
-    _refuse_tier_hits(feats)
+    serve = read_only_serves_tier()
+    if not serve:
+        _refuse_tier_hits(feats)
+    elif _tiered_feats(feats):
+        _refuse_tier_capture()      # (the missing keys' count is read on the host)
     with torch.no_grad():
         if _FUSED_ONEHOT:
-            out = _fused_onehot_readonly(feats, order, out_dtype)
+            out = _fused_onehot_readonly(feats, order, out_dtype, serve_tier=serve)
             if out is not None:
                 return out
         for i in range(0, len(feats), _lib.MAX_GROUP):
-            _prepare_readonly(feats[i:i + _lib.MAX_GROUP])
+            _prepare_readonly(feats[i:i + _lib.MAX_GROUP], serve_tier=serve)
         return _pool_all(feats, order, out_dtype=out_dtype)
 
 

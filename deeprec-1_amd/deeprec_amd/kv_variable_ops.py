@@ -275,6 +275,11 @@ def read_only_active():
     return getattr(_READ_ONLY, "depth", 0) > 0
 
 
+def read_only_serves_tier():
+    """Inside read_only_lookups(serve_tier=True), or a block nested in one."""
+    return read_only_active() and getattr(_READ_ONLY, "serve_tier", False)
+
+
 class read_only_lookups(object):
     """Context manager (re-entrant, per thread): inside it embedding_lookup,
     embedding_lookup_sparse[_multi] and safe_embedding_lookup_sparse read
@@ -284,14 +289,27 @@ class read_only_lookups(object):
     grad_fn and nothing is queued in pending_grads.  Dense tables and
     tensors behave as outside it.  The sharded lookup engines (sharded.py)
     follow it too: their owners serve without inserting, and an id its
-    owner does not serve reads that OWNER's default row."""
+    owner does not serve reads that OWNER's default row.
+
+    serve_tier=True (inherited by the blocks nested in it): the pooled
+    lookups of an HBM_DRAM EmbeddingVariable serve the ids its host-DRAM tier
+    holds from the tier, in place -- neither tier changes -- instead of
+    refusing the batch."""
+
+    def __init__(self, *, serve_tier=False):
+        self._serve_tier = bool(serve_tier)
+        self._outer = []
 
     def __enter__(self):
         _READ_ONLY.depth = getattr(_READ_ONLY, "depth", 0) + 1
+        outer = getattr(_READ_ONLY, "serve_tier", False)
+        self._outer.append(outer)
+        _READ_ONLY.serve_tier = outer or self._serve_tier
         return self
 
     def __exit__(self, *exc):
         _READ_ONLY.depth -= 1
+        _READ_ONLY.serve_tier = self._outer.pop()
         return False
 
 
@@ -1290,10 +1308,7 @@ class EmbeddingVariable(object):
         check(lib().dr_host_tier_take(p._tier, uniq.ctypes.data, uniq.size, 0, hit_idx.ctypes.data,
                                       vptr, None, fr.ctypes.data, cm.ctypes.data, C.byref(hits)))
         h = hits.value
-        need = np.uint32(1 | (1 << col))
-        ok = (cm[:h] & need) == need
-        if p.filter_freq:
-            ok &= fr[:h] >= p.filter_freq
+        ok = tier_rows_served(cm[:h], fr[:h], col, p.filter_freq)
         src_of_uniq = np.full(uniq.size, -1, np.int64)
         src_of_uniq[hit_idx[:h][ok]] = np.nonzero(ok)[0]
         src = src_of_uniq[inv.reshape(-1)]
@@ -1305,6 +1320,56 @@ class EmbeddingVariable(object):
             rows_scatter(block, torch.from_numpy(pos.astype(np.int32)).to(self.device),
                          out.view(torch.float32))
         return h
+
+    def _tier_serve_rows(self, miss):
+        """(keys, rows) this column serves read-only out of the host tier for
+        the host int64 keys `miss` (duplicates allowed): the keys distinct and
+        ascending as signed int64, rows[i] the stored row bytes of keys[i].
+        tier_rows_served decides; neither tier changes (take, erase=0)."""
+        import numpy as np
+        p = self._primary or self
+        col = self._slot_index
+        nb = self._col_bytes(self)
+        none = np.empty(0, np.int64), np.empty((0, nb), np.uint8)
+        with p._lock:
+            if not p._tier_n or col >= p._tier_ncols or miss.size == 0:
+                return none
+            miss = np.ascontiguousarray(miss)
+            # which of them the store holds (never-seen ids are most of a batch's
+            # misses): the row buffer below is sized by the hits alone
+            idx = np.empty(miss.size, np.int64)
+            hits = C.c_int64(0)
+            check(lib().dr_host_tier_take(p._tier, miss.ctypes.data, miss.size, 0, idx.ctypes.data,
+                                          None, None, None, None, C.byref(hits)))
+            if not hits.value:
+                return none
+            held = np.ascontiguousarray(miss[idx[:hits.value]])
+            n = held.size
+            rows = np.empty((n, nb), np.uint8)
+            fr, cm = np.empty(n, np.int64), np.empty(n, np.uint32)
+            vptr = (C.c_void_p * p._tier_ncols)()
+            vptr[col] = rows.ctypes.data
+            check(lib().dr_host_tier_take(p._tier, held.ctypes.data, n, 0, idx.ctypes.data, vptr,
+                                          None, fr.ctypes.data, cm.ctypes.data, C.byref(hits)))
+            h = hits.value
+        ok = np.nonzero(tier_rows_served(cm[:h], fr[:h], col, p.filter_freq))[0]
+        keys = held[idx[:h]][ok]
+        order = np.argsort(keys, kind="stable")     # distinct: the sort is np.unique's
+        return np.ascontiguousarray(keys[order]), np.ascontiguousarray(rows[:h][ok][order])
+
+
+def tier_rows_served(colmask, freq, col, filter_freq):
+    """Which entries of the host tier a read-only lookup of column `col`
+    serves, by the rule HBM applies (RoDesc, ev.hip): the primary's and the
+    column's first-touch bit set in the stored colmask -- the other bits,
+    DR_TIER_UPDATED among them, do not matter -- and, for a Counter EV
+    (filter_freq > 0), the stored freq >= filter_freq.  numpy in, bool mask out."""
+    import numpy as np
+    need = np.uint32(1 | (1 << int(col)))
+    ok = (np.asarray(colmask, np.uint32) & need) == need
+    if filter_freq:
+        ok &= np.asarray(freq, np.int64) >= int(filter_freq)
+    return ok
 
 
 def _mark_grouped(what, evs, xs, num_valid, launch):
@@ -1409,13 +1474,18 @@ def _tiered_items(evs, keys, num_valid):
         if getattr(p, "_tier_n", 0) and keys[t].numel():
             by_dev.setdefault(str(p.device), []).append(
                 (p, keys[t], None if num_valid is None else num_valid[t]))
-    if by_dev and _capturing():
+    if by_dev:
+        _refuse_tier_capture()
+    return by_dev
+
+
+def _refuse_tier_capture():
+    if _capturing():
         raise _lib.InvalidArgumentError(
             _lib.INVALID_ARGUMENT, "a lookup of an HBM_DRAM EmbeddingVariable whose host tier "
             "holds keys cannot be captured in a graph: which keys to promote is read on the "
             "host at every call (run the lookup outside the capture, or capture while the "
             "tier is empty)")
-    return by_dev
 
 
 def promote_grouped(evs, keys, num_valid=None):
@@ -1490,6 +1560,96 @@ def tier_hits(evs, keys, num_valid=None):
                                                   None, None, None, None, C.byref(h)))
                 hits += h.value
     return hits
+
+
+class TierOverlay(object):
+    """What the host tier serves for one group's batch (tier_serve_overlay)."""
+
+    def __init__(self, keys, off, blob, row_bytes, miss_keys, miss_pos):
+        self.keys = keys              # device int64[M], ascending inside each table's range
+        self.off = off                # host prefix, T + 1 entries
+        self.blob = blob              # device uint8: the M rows, table after table
+        self.row_bytes = row_bytes    # per table
+        self.miss_keys = miss_keys    # device: dr_ev_missing_keys' list (m entries)
+        self.miss_pos = miss_pos
+
+    def off_array(self):
+        return (C.c_int64 * len(self.off))(*self.off)
+
+    def rows(self, t, dtype):
+        """Table t's served rows, [n_t, dim] of the EV's value type."""
+        b0 = sum((self.off[u + 1] - self.off[u]) * self.row_bytes[u] for u in range(t))
+        n = self.off[t + 1] - self.off[t]
+        return self.blob[b0:b0 + n * self.row_bytes[t]].view(dtype).view(n, -1)
+
+
+_ZERO_COUNT = {}
+
+
+def tier_serve_overlay(evs, keys, num_valid=None, koff=None):
+    """The overlay a read-only pooled lookup serves from the host tier, for one
+    group: evs[t] (<= MAX_GROUP columns on one device, tiered or not) is looked
+    up at keys[t] (the first num_valid[t] of them: device int64[1]) -- or, with
+    the host prefix `koff`, at keys[koff[t]:koff[t + 1]] of the one flat device
+    tensor `keys`.  One dr_ev_missing_keys and one host read of its count; only
+    the keys HBM does not hold come to the host, where each EV's store gives
+    the rows it serves (EmbeddingVariable._tier_serve_rows).  None when every
+    tier is empty (nothing is launched), when HBM holds the whole batch, or
+    when the tier serves none of the missing keys: the lookup then runs as
+    without a tier.  Neither tier changes."""
+    import numpy as np
+    T = len(evs)
+    prim = [getattr(ev, "_primary", None) or ev for ev in evs]
+    if koff is None:
+        dev = prim[0].device
+        ks = [k.reshape(-1).to(device=dev, dtype=torch.int64) for k in keys]
+        koff = [0]
+        for k in ks:
+            koff.append(koff[-1] + k.numel())
+    else:
+        ks = None
+    tiered = [bool(getattr(p, "_tier_n", 0)) and koff[t + 1] > koff[t]
+              for t, p in enumerate(prim)]
+    if not any(tiered):
+        return None
+    _refuse_tier_capture()
+    dev = prim[0].device
+    flat = keys if ks is None else (ks[0].contiguous() if T == 1 else torch.cat(ks))
+    total = koff[-1]
+    mk = torch.empty(total, dtype=torch.int64, device=dev)
+    mp = torch.empty(total, dtype=torch.int64, device=dev)
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)
+    nd = [None if num_valid is None or num_valid[t] is None else num_valid[t].data_ptr()
+          for t in range(T)]
+    if not all(tiered):
+        # the other tables of the group take no part: a device count of zero
+        z = _ZERO_COUNT.get(str(dev))
+        if z is None:
+            z = _ZERO_COUNT[str(dev)] = torch.zeros(1, dtype=torch.int64, device=dev)
+        nd = [n if tiered[t] else z.data_ptr() for t, n in enumerate(nd)]
+    handles = (C.c_void_p * T)(*[p._h.value for p in prim])
+    ckoff = (C.c_int64 * (T + 1))(*koff)
+    check(lib().dr_ev_missing_keys(handles, T, ptr(flat), ckoff, (C.c_void_p * T)(*nd), ptr(mk),
+                                   ptr(mp), ptr(cnt), stream_handle(dev)))
+    m = int(cnt.item())     # the call's one synchronise
+    if m == 0:
+        return None
+    mk, mp = mk[:m], mp[:m]
+    hk, hp = mk.cpu().numpy(), mp.cpu().numpy()
+    tab = np.searchsorted(np.asarray(koff[1:], np.int64), hp, side="right")
+    okeys, orows, off, nbs = [], [], [0], []
+    for t, ev in enumerate(evs):
+        nbs.append(ev._col_bytes(ev))
+        if tiered[t]:
+            k, r = ev._tier_serve_rows(hk[tab == t])
+            if k.size:
+                okeys.append(k)
+                orows.append(r.reshape(-1))
+        off.append(sum(x.size for x in okeys))
+    if not okeys:
+        return None
+    return TierOverlay(torch.from_numpy(np.concatenate(okeys)).to(dev), off,
+                       torch.from_numpy(np.concatenate(orows)).to(dev), nbs, mk, mp)
 
 
 def refuse_tiered_evs(evs, what):

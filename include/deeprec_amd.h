@@ -909,6 +909,38 @@ int dr_host_tier_shrink_keys(dr_host_tier* t, int64_t global_step, int64_t steps
                              int64_t* keys_out, int64_t capacity,
                              int64_t* removed /* nullable */);
 
+/* Serving pooled read-only lookups from the host tier in place (DESIGN     */
+/* section 19).  The overlay is what the host fetched for one batch:        */
+/* ov_keys[M] (device), strictly ascending as signed int64 inside table t's */
+/* range ov_off_host[t] .. ov_off_host[t + 1] (a range may be empty), and   */
+/* ov_rows[M, row words] in the EVs' value type.  Both entries read the     */
+/* overlay alone -- no table is touched -- launch one kernel, and neither   */
+/* allocate nor synchronise.  A null pointer (n_dev_per_table excepted) is  */
+/* DR_INVALID_ARGUMENT.                                                     */
+/* After dr_ev_find_grouped (its keys, koff_host and n_dev_per_table):      */
+/* rows_inout[i] >= 0 stays; a negative entry becomes -(2 + j) when keys[i] */
+/* is ov_keys[j] of its table's range (j the global index), else -1.        */
+/* Entries past *n_dev_per_table[t] are not written.                        */
+int dr_ev_overlay_resolve(const int64_t* keys, const int64_t* koff_host,
+                          const int64_t* const* n_dev_per_table /* nullable */, int num_tables,
+                          const int64_t* ov_keys, const int64_t* ov_off_host,
+                          int64_t* rows_inout, void* stream);
+/* After dr_ev_lookup_onehot_readonly over the feature-major ids            */
+/* keys[koff_host[t] + b] (every table `batch` ids): entry i < m of         */
+/* dr_ev_missing_keys' list (device) names position miss_pos[i] = koff[t] + */
+/* b; when the overlay of table t holds miss_keys[i], its row is written to */
+/* out[b * out_stride + t * dim ..] exactly as the fused kernel writes a    */
+/* row (order, DR_LOOKUP_OUT_BF16: the same helpers).  dim and out_stride   */
+/* count elements of the output type; row_words = float words of an overlay */
+/* row (dim for fp32 rows, dim / 2 for bf16 rows), % 4 == 0 and <= 256;     */
+/* out and ov_rows 16-B aligned.  Duplicate entries write identical bytes;  */
+/* a position outside [0, koff_host[T]) is skipped.                         */
+int dr_ev_overlay_patch_onehot(const int64_t* miss_keys, const int64_t* miss_pos, int64_t m,
+                               const int64_t* koff_host, int num_tables, const int64_t* ov_keys,
+                               const int64_t* ov_off_host, const void* ov_rows,
+                               int64_t row_words, void* out, int64_t out_stride, int64_t dim,
+                               int order, int flags, void* stream);
+
 /* Per-key freq / version of the primary, host-side, syncs (tests/debug).   */
 int dr_ev_key_meta(dr_ev* ev, const int64_t* keys_host, int64_t n, int64_t* freq_host,
                    int64_t* version_host, int32_t* has_row_host, void* stream);
