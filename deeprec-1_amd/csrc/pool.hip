@@ -16,6 +16,7 @@
 //             (core/kernels/fused_embedding/fused_embedding_local_ops_gpu.cu.cc:41-84)
 // fp32 adds are separate roundings (built with -ffp-contract=off).
 #include "dr_common.h"
+#include "dr_pool_order.h"
 #include "dr_rows.h"
 
 namespace dr {
@@ -164,44 +165,10 @@ __device__ __forceinline__ void pool_bag_rows(const dr_pool_desc& d, int64_t num
     store_any<VEC, G, CPL, OB>(acc, out, lg, dv);
     return;
   }
-  // ORDER_ALI
-  if (num == 1) {
-    fetch_p<VEC, G, CPL, ORDER, BF>(acc, P(0), d.max_norm, lg, dv);
-    store_any<VEC, G, CPL, OB>(acc, out, lg, dv);
-    return;
-  }
-  int64_t r = num % 8;
-  if (r == 0) r = 8;
-  if (r == 1) r = 9;
-  {
-    R x[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j)
-      if (j < r) fetch_p<VEC, G, CPL, ORDER, BF>(x[j], P(j), d.max_norm, lg, dv);
-    acc = x[0];
-#pragma unroll
-    for (int j = 1; j < 9; ++j)
-      if (j < r) acc_add(acc, x[j]);
-  }
-  if (num < 10 && d.combiner != DR_COMBINER_SUM) {
-    const float m = d.combiner == DR_COMBINER_MEAN ? (float)num : (float)sqrt((double)num);
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) acc.v[c] = vdiv(acc.v[c], m);
-  }
-  for (int64_t g = r; g < num; g += 8) {
-    R x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fetch_p<VEC, G, CPL, ORDER, BF>(x[j], P(g + j), d.max_norm, lg, dv);
-    R s = x[0];
-#pragma unroll
-    for (int j = 1; j < 8; ++j) acc_add(s, x[j]);
-    acc_add(acc, s);
-  }
-  if (num >= 10 && d.combiner != DR_COMBINER_SUM) {
-    const float q = d.combiner == DR_COMBINER_MEAN ? (float)num : (float)sqrt((double)num);
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) acc.v[c] = vdiv(acc.v[c], q);
-  }
+  // ORDER_ALI: the order itself is dr_pool_order.h's, over the row functor
+  ali_bag_rows<VEC, G, CPL>(acc, num, d.combiner, [&](R& x, int64_t k) {
+    fetch_p<VEC, G, CPL, ORDER, BF>(x, P(k), d.max_norm, lg, dv);
+  });
   store_any<VEC, G, CPL, OB>(acc, out, lg, dv);
 }
 
@@ -213,11 +180,8 @@ __device__ void pool_bag(const dr_pool_desc& d, int64_t b, int dim, int lg, int 
   const int64_t k0 = d.bag_off[b];
   const int64_t num = (int64_t)d.bag_off[b + 1] - k0;
   float* out = d.out + b * d.out_stride;
-  // an empty bag is a zero row -- except with weights and mean / sqrtn,
-  // where the reference divides the zero segment_sum by a zero weight sum
-  // (embedding_ops.py:636-645): 0 / 0 = NaN, which the weights branch
-  // below reproduces
-  if (num <= 0 && !(d.weights && d.combiner != DR_COMBINER_SUM)) {
+  // (the empty-bag rule and the weighted order: dr_pool_order.h)
+  if (bag_is_zero(num, d.weights, d.combiner)) {
     R z;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) z.v[c] = vzero<typename VecT<VEC>::T>();
@@ -227,22 +191,9 @@ __device__ void pool_bag(const dr_pool_desc& d, int64_t b, int dim, int lg, int 
   if (d.weights) {
     // embedding_ops.py:609-651: gather * w, segment_sum, / sum(w) or sqrt(sum(w^2))
     R acc;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) acc.v[c] = vzero<typename VecT<VEC>::T>();
-    float wsum = 0.f;
-    for (int64_t k = 0; k < num; ++k) {
-      R x;
+    bag_rows_weighted<VEC, G, CPL>(acc, num, d.combiner, d.weights + k0, [&](R& x, int64_t k) {
       fetch<VEC, G, CPL, ORDER, BF>(x, d, k0 + k, dim, lg, dv, st);
-      const float w = d.weights[k0 + k];
-#pragma unroll
-      for (int c = 0; c < CPL; ++c) acc.v[c] = vadd(acc.v[c], vmul(x.v[c], w));
-      wsum = wsum + (d.combiner == DR_COMBINER_SQRTN ? w * w : w);
-    }
-    if (d.combiner != DR_COMBINER_SUM) {
-      const float q = d.combiner == DR_COMBINER_SQRTN ? sqrtf(wsum) : wsum;
-#pragma unroll
-      for (int c = 0; c < CPL; ++c) acc.v[c] = vdiv(acc.v[c], q);
-    }
+    });
     store_any<VEC, G, CPL, OB>(acc, out, lg, dv);
     return;
   }

@@ -15,8 +15,9 @@ from .embedding_ops import (DenseTable, SparseTensor, embedding_lookup, embeddin
                             safe_embedding_lookup_sparse)
 from .kv_variable_ops import (CBFFilter, CounterFilter, EmbeddingVariable, EmbeddingVariableOption,
                               GlobalStepEvict, IndexedSlices, InitializerOption, KeyBudgetEvict,
-                              StorageOption, StorageType, flush_releases, get_embedding_variable,
-                              read_only_lookups, read_only_serves_tier)
+                              MultiHashVariable, MultiHashVariableConfig, StorageOption,
+                              StorageType, flush_releases, get_embedding_variable,
+                              get_multihash_variable, read_only_lookups, read_only_serves_tier)
 from .ops import set_validate, status_check
 from .string_ops import StringTensor, string_to_hash_bucket_fast
 from .training import (AdagradDecayOptimizer, AdagradOptimizer, AdamAsyncOptimizer, AdamOptimizer,
@@ -31,5 +32,6 @@ __all__ = [
     "AdagradOptimizer", "AdagradDecayOptimizer", "AdamAsyncOptimizer", "AdamOptimizer",
     "FtrlOptimizer", "GradientDescentOptimizer", "StringTensor",
     "string_to_hash_bucket_fast", "StorageOption", "StorageType", "InitializerOption",
-    "read_only_serves_tier",
+    "read_only_serves_tier", "MultiHashVariable", "MultiHashVariableConfig",
+    "get_multihash_variable",
 ]

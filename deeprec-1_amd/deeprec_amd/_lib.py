@@ -79,6 +79,20 @@ class DrPoolGradDesc(C.Structure):
     ]
 
 
+MHV_OPERATIONS = {"add": 0, "mul": 1, "concat": 2}    # DR_MHV_*
+
+
+class DrMhvDesc(C.Structure):
+    """dr_mhv_desc (include/deeprec_amd.h): one multi-hash feature's pooled lookup."""
+    _fields_ = [
+        ("q_table", C.c_void_p), ("q_rows", C.c_int64), ("r_table", C.c_void_p),
+        ("r_rows", C.c_int64), ("q_dim", C.c_int32), ("r_dim", C.c_int32),
+        ("operation", C.c_int32), ("combiner", C.c_int32), ("ids", C.c_void_p),
+        ("bag_off", C.c_void_p), ("weights", C.c_void_p), ("out", C.c_void_p),
+        ("out_stride", C.c_int64),
+    ]
+
+
 class DrEvConfig(C.Structure):
     _fields_ = [
         ("dim", C.c_int64), ("capacity", C.c_int64), ("steps_to_live", C.c_int64),
@@ -405,6 +419,10 @@ SIGNATURES = {
                                     _P, _P, _P, _P, _SZ, _P]),
     "dr_fill_synthetic": (_I32, [_P, _I64, _I32, _U64, _P]),
     "dr_synth_value": (_F32, [_U64, _I64, _I64]),
+    "dr_mhv_lookup_sparse_grouped": (_I32, [_P, _I32, _I64, _P]),
+    "dr_mhv_gather": (_I32, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P]),
+    "dr_mhv_grad": (_I32, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P, _P,
+                           _P]),
 }
 
 _lib = None

@@ -17,8 +17,9 @@ import torch
 
 from . import _lib, ops
 from ._lib import COMBINERS, ORDER_ALI, ORDER_SEQ, DrPoolDesc, check, lib, ptr, stream_handle, workspace
-from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
-                               _refuse_tier_capture, promote_grouped, read_only_active,
+from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, MultiHashVariable,
+                               PendingRowSlices, _refuse_tier_capture, promote_grouped,
+                               read_only_active,
                                read_only_serves_tier, tier_hits, tier_serve_overlay)
 
 
@@ -89,6 +90,8 @@ class _Feature(object):
     sp_ids.indices (read in place, stride 2: no per-step conversion)."""
 
     def __init__(self, params, values, seg, batch, weights, combiner, max_norm, onehot=False):
+        if isinstance(params, MultiHashVariable) and max_norm is not None:
+            _refuse_mhv("max_norm (the reference clips each sub-lookup; not built)")
         vd = getattr(params, "value_dtype", torch.float32)
         if vd != torch.float32 and not (vd == torch.bfloat16 and isinstance(params,
                                                                            EmbeddingVariable)):
@@ -143,6 +146,16 @@ class _Feature(object):
             s = self.seg64 if self.seg_stride == 1 else self.seg64[:, 0]
             self._seg32 = s.to(torch.int32).contiguous()
         return self._seg32
+
+
+def _refuse_mhv(what):
+    raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
+                                    "a MultiHashVariable does not take " + what)
+
+
+def _has_mhv(params):
+    ps = params if isinstance(params, (list, tuple)) else [params]
+    return any(isinstance(p, MultiHashVariable) for p in ps)
 
 
 def _tiered_feats(feats):
@@ -350,8 +363,40 @@ def _queue_grads(feats, g, col0, total, tensors=()):
             for x, sl in zip(grp.feats, sls):
                 x.params.pending_grads.append(sl)
             continue
+        if isinstance(holder, MultiHashVariable):
+            _mhv_queue(holder, _grad_to_slices(f, g, cols[i], total))
+            continue
         holder.pending_grads.append(_grad_to_slices(f, g, cols[i], total))
     return dense
+
+
+def _mhv_tables(p):
+    """(Q weight, R weight, C arguments up to the operation) of a MultiHashVariable."""
+    q, r = p.val_list[0].weight, p.val_list[1].weight
+    return q, r, (ptr(q), q.shape[0], q.shape[1], ptr(r), r.shape[0], r.shape[1],
+                  _lib.MHV_OPERATIONS[p.operation])
+
+
+def _mhv_queue(p, sl):
+    """The per-unique-id gradient of a multi-hash lookup (IndexedSlices over
+    the raw ids) -> the two tables' IndexedSlices (dr_mhv_grad), queued on
+    them.  Their indices q(uniq) / r(uniq) repeat: the optimizer's business."""
+    q, r, targs = _mhv_tables(p)
+    uniq = sl.indices.contiguous()
+    gu = sl.values.contiguous()
+    n = uniq.numel()
+    dev = uniq.device
+    qi = torch.empty(n, dtype=torch.int64, device=dev)
+    ri = torch.empty(n, dtype=torch.int64, device=dev)
+    qv = torch.empty((n, q.shape[1]), dtype=torch.float32, device=dev)
+    # add: both slices carry gU itself, one block serves both
+    rv = qv if p.operation == "add" else torch.empty((n, r.shape[1]), dtype=torch.float32,
+                                                      device=dev)
+    check(lib().dr_mhv_grad(*targs, ptr(uniq), ptr(gu), n, ptr(sl.num_valid), ptr(qi), ptr(ri),
+                            ptr(qv), ptr(rv), stream_handle(dev)))
+    ops._post(dev)
+    p.val_list[0].pending_grads.append(IndexedSlices(qv, qi, sl.num_valid, False))
+    p.val_list[1].pending_grads.append(IndexedSlices(rv, ri, sl.num_valid, False))
 
 
 class _StackFn(torch.autograd.Function):
@@ -384,6 +429,8 @@ def embedding_stack(x0, params_list, sp_ids_list, combiner="sum"):
         raise _lib.DeepRecError(_lib.INVALID_ARGUMENT,
                                 "embedding_stack builds the fp32 dot-interaction input; "
                                 "bf16 EVs: embedding_lookup_sparse_multi")
+    if _has_mhv(list(params_list)):
+        _refuse_mhv("embedding_stack (use embedding_lookup_sparse_multi)")
     feats = []
     for p, sp in zip(params_list, sp_ids_list):
         v = sp.values.to(torch.int64).contiguous()
@@ -1060,8 +1107,18 @@ def _pool_all(feats, order, out=None, out_dtype=None):
     i = 0
     while i < len(feats):
         j = i
-        while j < len(feats) and dims[j] == dims[i] and j - i < _lib.MAX_GROUP:
+        mh = isinstance(feats[i].params, MultiHashVariable)
+        while (j < len(feats) and j - i < _lib.MAX_GROUP
+               and isinstance(feats[j].params, MultiHashVariable) == mh
+               and (mh or dims[j] == dims[i])):
             j += 1
+        if mh:
+            # multi-hash features (any dims and operations) go to their own
+            # grouped entry, into their column slices of the same output
+            _pool_mhv(feats[i:j], out, col, stride, odt)
+            col += sum(dims[i:j])
+            i = j
+            continue
         onehot = all(f.onehot for f in feats[i:j])
         if not onehot:
             _bag_offsets_all(feats[i:j])
@@ -1075,6 +1132,30 @@ def _pool_all(feats, order, out=None, out_dtype=None):
         col = c
         i = j
     return out
+
+
+def _pool_mhv(feats, out, col, stride, odt):
+    """dr_mhv_lookup_sparse_grouped over <= MAX_GROUP multi-hash features:
+    feature t's pooled rows land at columns [col_t, col_t + dim_t) of out."""
+    if odt != torch.float32:
+        _refuse_mhv("a %s output (its tables are float32)" % (odt,))
+    dev = out.device
+    _bag_offsets_all(feats, skip_onehot=True)
+    descs = (_lib.DrMhvDesc * len(feats))()
+    for d, f in zip(descs, feats):
+        p = f.params
+        (d.q_table, d.q_rows, d.q_dim, d.r_table, d.r_rows, d.r_dim,
+         d.operation) = _mhv_tables(p)[2]
+        d.combiner = COMBINERS[f.combiner]
+        d.ids = ptr(f.values)
+        d.bag_off = None if f.onehot else ptr(f.bag_off)
+        d.weights = ptr(f.weights)
+        d.out = out.data_ptr() + 4 * col
+        d.out_stride = stride
+        col += p.dim
+    check(lib().dr_mhv_lookup_sparse_grouped(descs, len(feats), feats[0].batch,
+                                             stream_handle(dev)))
+    ops._post(dev)
 
 
 def _seg_of(sp_ids):
@@ -1093,6 +1174,12 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
         combiner = "mean"
     if combiner not in ("mean", "sqrtn", "sum", "tile"):
         raise ValueError("combiner must be one of 'mean', 'sqrtn', 'sum' or 'tile'")
+    if _has_mhv(params):
+        if combiner == "tile":
+            _refuse_mhv("combiner=\"tile\"")
+        if isinstance(params, (list, tuple)) and len(params) != 1:
+            raise TypeError("a MultiHashVariable is not partitioned: pass the variable itself, "
+                            "not a list of partitions")
     if combiner == "tile":
         return _tile_lookup_sparse(params if isinstance(params, (list, tuple)) else [params],
                                    sp_ids, sp_weights, partition_strategy, max_norm)
@@ -1128,6 +1215,13 @@ def embedding_lookup(params, ids, partition_strategy="mod", name=None, max_norm=
     """tf.nn.embedding_lookup (embedding_ops.py:94-342, 346)."""
     if isinstance(params, (list, tuple)) and len(params) == 1:
         params = params[0]
+    if _has_mhv(params):
+        if isinstance(params, (list, tuple)):
+            raise TypeError("a MultiHashVariable is not partitioned: pass the variable itself, "
+                            "not a list of partitions")
+        if max_norm is not None:
+            _refuse_mhv("max_norm (the reference clips each sub-lookup; not built)")
+        return _mhv_gather(params, ids)
     if isinstance(params, (list, tuple)):
         flat = ids.reshape(-1).to(torch.int64).contiguous()
         init = None
@@ -1148,6 +1242,19 @@ def embedding_lookup(params, ids, partition_strategy="mod", name=None, max_norm=
         r2 = r2 * max_norm / torch.maximum(l2, torch.tensor(max_norm, device=r2.device))
         res = r2.reshape(res.shape)
     return res
+
+
+def _mhv_gather(p, ids, n_dev=None):
+    """embedding_lookup over a MultiHashVariable: ids.shape + [dim] combined
+    rows (dr_mhv_gather; n_dev: device count of the ids, rows past it are
+    left unwritten)."""
+    flat = ids.reshape(-1).to(torch.int64).contiguous()
+    dev = ops._dev(flat)
+    out = torch.empty((flat.numel(), p.dim), dtype=torch.float32, device=dev)
+    check(lib().dr_mhv_gather(*_mhv_tables(p)[2], ptr(flat), flat.numel(), ptr(n_dev), ptr(out),
+                              stream_handle(dev)))
+    ops._post(dev)
+    return out.reshape(tuple(ids.shape) + (p.dim,))
 
 
 def _partition_plan(params, flat, n_dev, partition_strategy):
@@ -1482,6 +1589,9 @@ def fused_embedding_lookup_sparse(embedding_weights, sparse_ids, combiner=None, 
         if isinstance(p, EmbeddingVariable):
             raise TypeError("fused_embedding_lookup_sparse takes dense tables (the reference's "
                             "fused ops do not support EmbeddingVariables)")
+        if isinstance(p, MultiHashVariable):
+            raise TypeError("fused_embedding_lookup_sparse takes dense tables, not a "
+                            "MultiHashVariable (embedding_lookup_sparse fuses its lookup)")
     tensors = [p for p in parts if torch.is_tensor(p) and p.requires_grad] \
         if torch.is_grad_enabled() else []
     anchors = [_anchor(p) for p in parts if isinstance(p, DenseTable)] \

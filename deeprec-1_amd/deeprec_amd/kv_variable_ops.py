@@ -1652,10 +1652,20 @@ def tier_serve_overlay(evs, keys, num_valid=None, koff=None):
                        torch.from_numpy(np.concatenate(orows)).to(dev), nbs, mk, mp)
 
 
+def refuse_multihash(evs, what):
+    """The sharded engines shard EmbeddingVariables by key; a MultiHashVariable
+    has no keys to shard (its two tables are small enough to replicate)."""
+    for ev in evs or ():
+        if isinstance(ev, MultiHashVariable):
+            raise TypeError("%s shards EmbeddingVariables; %s is a MultiHashVariable (look it "
+                            "up locally with embedding_lookup_sparse)" % (what, ev.name))
+
+
 def refuse_tiered_evs(evs, what):
     """For the entry points that read or create keys in HBM without promoting
     (the sharded engines): a tiered EV would be served defaults for the keys
     its host tier holds, so it is refused."""
+    refuse_multihash(evs, what)
     for ev in evs or ():    # (an engine built without local EVs has none to refuse)
         if getattr(ev, "tiered", False):
             raise _lib.InvalidArgumentError(
@@ -1691,3 +1701,114 @@ def get_embedding_variable(name, embedding_dim, key_dtype=torch.int64, initializ
 
 def reset_registry():
     _EV_REGISTRY.clear()
+
+
+# ---------------------------------------------------------------------------
+# MultiHashVariable (kv_variable_ops.py:768 MultiHashVariable,
+# variable_scope.py get_multihash_variable), "Q-R" strategy
+# ---------------------------------------------------------------------------
+class MultiHashVariableConfig(object):
+    """size = [[Q, Dq], [R, Dr]], strategy "Q-R", operation add / mul / concat."""
+
+    def __init__(self, size, strategy="Q-R", operation="add"):
+        if strategy != "Q-R":
+            raise ValueError("complementary_strategy %r: only \"Q-R\" is built" % (strategy,))
+        if operation not in _lib.MHV_OPERATIONS:
+            raise ValueError("operation %r: must be one of 'add', 'mul' or 'concat'"
+                             % (operation,))
+        try:
+            size = [[int(x) for x in pair] for pair in size]
+        except (TypeError, ValueError):
+            size = None
+        if (size is None or len(size) != 2 or any(len(p) != 2 for p in size)
+                or any(x < 1 for p in size for x in p)):
+            raise ValueError("dims must be [[Q, Dq], [R, Dr]] with rows >= 1 and dim >= 1")
+        if operation != "concat" and size[0][1] != size[1][1]:
+            raise ValueError("dims: operation %r needs Dq == Dr (got %d and %d)"
+                             % (operation, size[0][1], size[1][1]))
+        self.size = size
+        self.strategy = strategy
+        self.operation = operation
+
+
+class MultiHashVariable(object):
+    """Two small dense tables standing for one large one (the quotient-
+    remainder trick): id -> Q[id // Q_rows] (op) R[id % R_rows], the divisor
+    of the quotient being the Q table's row count (csrc/dr_multihash.h holds
+    the rule).  val_list = [Q table, R table] (DenseTables, fp32); the pooled
+    and unpooled lookups of embedding_ops combine the two rows inside the
+    kernel, and the backward queues IndexedSlices on both tables."""
+
+    def __init__(self, name, val_list, mhvconfig):
+        if len(val_list) != 2:
+            raise ValueError("val_list must hold the Q and the R table")
+        for t, (rows, dim) in zip(val_list, mhvconfig.size):
+            if t.weight.dtype != torch.float32:
+                raise TypeError("MultiHashVariable %s: tables must be float32 (got %s)"
+                                % (name, t.weight.dtype))
+            if tuple(t.weight.shape) != (rows, dim):
+                raise ValueError("MultiHashVariable %s: table shape %s does not match dims %s"
+                                 % (name, tuple(t.weight.shape), [rows, dim]))
+        if val_list[0].device != val_list[1].device:
+            raise ValueError("MultiHashVariable %s: both tables must be on one device" % name)
+        self.name = name
+        self._val_list = list(val_list)
+        self.mhvconfig = mhvconfig
+        self.device = val_list[0].device
+        (_, dq), (_, dr) = mhvconfig.size
+        self.dim = dq + dr if mhvconfig.operation == "concat" else dq
+
+    @property
+    def val_list(self):
+        return self._val_list
+
+    @property
+    def operation(self):
+        return self.mhvconfig.operation
+
+    def get_shape(self):
+        """(ids with a valid quotient, dim): the table the variable stands for."""
+        q_rows = self.mhvconfig.size[0][0]
+        return (q_rows * q_rows, self.dim)
+
+
+def _mhv_table(name, initializer, rows, dim, device):
+    from .embedding_ops import DenseTable
+    if initializer is None:
+        initializer = 0.0
+    if torch.is_tensor(initializer):
+        if initializer.dtype != torch.float32:
+            raise TypeError("%s: the tables are float32 (initializer is %s)"
+                            % (name, initializer.dtype))
+        if tuple(initializer.shape) != (rows, dim):
+            raise ValueError("%s: initializer shape %s, table shape %s"
+                             % (name, tuple(initializer.shape), (rows, dim)))
+        w = initializer.detach().clone()
+    elif callable(initializer):
+        w = torch.as_tensor(initializer((rows, dim)))
+        if w.dtype != torch.float32:
+            raise TypeError("%s: the tables are float32 (initializer gave %s)" % (name, w.dtype))
+        w = w.reshape(rows, dim).clone()
+    else:
+        w = torch.full((rows, dim), float(initializer), dtype=torch.float32)
+    t = DenseTable(w.to(device))
+    t.name = name
+    return t
+
+
+def get_multihash_variable(name, dims, complementary_strategy="Q-R", operation="add",
+                           initializer=None, device=None):
+    """tf.get_multihash_variable (variable_scope.py) without partitioners.
+
+    dims = [[Q, Dq], [R, Dr]].  initializer: a callable given each table's
+    shape, a tensor taken as is (both tables of its shape), a scalar, or a pair
+    of those (Q's, R's); default as an EmbeddingVariable's default row, 0."""
+    cfg = MultiHashVariableConfig(dims, complementary_strategy, operation)
+    dev = torch.device(device) if device is not None else \
+        torch.device("cuda", torch.cuda.current_device())
+    inits = list(initializer) if isinstance(initializer, (list, tuple)) else [initializer] * 2
+    if len(inits) != 2:
+        raise ValueError("initializer: one value, or a pair (Q's, R's)")
+    tables = [_mhv_table("%s/%s" % (name, part), init, rows, dim, dev)
+              for part, init, (rows, dim) in zip("QR", inits, cfg.size)]
+    return MultiHashVariable(name, tables, cfg)

@@ -14,9 +14,21 @@ import torch
 from . import ops
 from ._lib import check, lib, ptr, stream_handle
 from .embedding_ops import DenseTable
-from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, PendingRowSlices,
-                              _flush_deferred_releases, _mark_updated_hbm,
+from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, MultiHashVariable,
+                              PendingRowSlices, _flush_deferred_releases, _mark_updated_hbm,
                               mark_updated_rows_grouped)
+
+
+def _expand_multihash(var_list):
+    """A MultiHashVariable in var_list stands for its two tables (each once)."""
+    if not any(isinstance(var, MultiHashVariable) for var in var_list):
+        return var_list
+    out = []
+    for var in var_list:
+        for v in (var.val_list if isinstance(var, MultiHashVariable) else [var]):
+            if all(v is not o for o in out):
+                out.append(v)
+    return out
 
 
 def _concat(slices):
@@ -120,6 +132,7 @@ class _Optimizer(object):
 
     def apply_gradients(self, var_list, global_step=None):
         gs = -1 if global_step is None else int(global_step)
+        var_list = _expand_multihash(var_list)
         late = self._record_updates(var_list)
         if self._opt == 0 and _KNOWN_ROWS:
             self._apply_fused_rows(var_list, gs)

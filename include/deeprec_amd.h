@@ -1776,6 +1776,73 @@ int dr_embedding_lookup_sparse_readonly(dr_ev* ev, const float* table, int64_t t
                                         size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* MultiHashVariable, "Q-R" (quotient-remainder) strategy: an id selects row */
+/* q = floordiv(id, q_rows) of the Q table and row r = floormod(id, r_rows)  */
+/* of the R table (int64 floor semantics; the quotient's divisor is the Q    */
+/* table's row count; csrc/dr_multihash.h holds the rule), and its embedding */
+/* row is Q[q] + R[r], Q[q] * R[r] (one fp32 operation per element, q_dim == */
+/* r_dim) or [Q[q] ; R[r]] (q_dim + r_dim columns).  r is always a valid     */
+/* row; an id whose q is outside [0, q_rows) contributes a zero row and       */
+/* latches DR_INVALID_ARGUMENT (as an out-of-range id of a dense table);      */
+/* nothing is read outside either table.  Both tables are fp32, row-major.   */
+/* None of the three entries allocates, synchronises or reads anything back: */
+/* they are legal under stream capture.  Null or inconsistent arguments are  */
+/* DR_INVALID_ARGUMENT before any launch.                                    */
+/* ------------------------------------------------------------------------ */
+#ifndef DR_MHV_ADD
+#define DR_MHV_ADD 0
+#define DR_MHV_MUL 1
+#define DR_MHV_CONCAT 2
+#endif
+typedef struct {
+  const float* q_table;    /* [q_rows, q_dim]                               */
+  int64_t q_rows;
+  const float* r_table;    /* [r_rows, r_dim]                               */
+  int64_t r_rows;
+  int32_t q_dim;
+  int32_t r_dim;
+  int32_t operation;       /* DR_MHV_*                                      */
+  int32_t combiner;        /* DR_COMBINER_*                                 */
+  const int64_t* ids;      /* [nnz] raw ids                                 */
+  const int32_t* bag_off;  /* [B+1] CSR offsets of the bags, or NULL: bag b */
+                           /* holds exactly nnz b (one-hot, nnz == B; then  */
+                           /* weights must be NULL)                         */
+  const float* weights;    /* [nnz] sp_weights or NULL                      */
+  float* out;              /* [B, out_stride]; the feature's dim columns    */
+  int64_t out_stride;
+} dr_mhv_desc;
+
+/* Pooled lookup of up to DR_MAX_GROUP features in one call: bag b of feature */
+/* t is reduced in the DR_ORDER_ALI association order over the combined rows */
+/* -- bit for bit what dr_pool_grouped returns over a table that holds them  */
+/* -- and written to out[b * out_stride + 0 .. dim).  DR_MHV_CONCAT is two    */
+/* independent pooled lookups (of Q by q at column 0, of R by r at column    */
+/* q_dim).  Features of one call may differ in shape and operation; those of */
+/* equal row shape share a launch.  Row widths as dr_pool_grouped: up to     */
+/* 1024 floats when the width is a multiple of 4 and the tables, `out` and   */
+/* out_stride are 16-byte aligned, else up to 256.                           */
+int dr_mhv_lookup_sparse_grouped(const dr_mhv_desc* descs_host, int num_tables, int64_t batch,
+                                 void* stream);
+/* Unpooled lookup: out[i] = combined row of ids[i], i < min(n, *n_dev)      */
+/* (n_dev: DEVICE count or NULL; rows past it are not written).  out is      */
+/* [n, dim] dense, dim = q_dim (add / mul) or q_dim + r_dim (concat).        */
+int dr_mhv_gather(const float* q_table, int64_t q_rows, int q_dim, const float* r_table,
+                  int64_t r_rows, int r_dim, int operation, const int64_t* ids, int64_t n,
+                  const int64_t* n_dev, float* out, void* stream);
+/* Gradient split: the per-unique-id gradient gu [n, dim] of the ids uniq [n] */
+/* becomes the two IndexedSlices of the reference's graph: q_idx / r_idx [n]  */
+/* = q(uniq) / r(uniq) (repeats are expected), q_val [n, q_dim] and r_val     */
+/* [n, r_dim] = gu, gu (add); gu * R[r], gu * Q[q] (mul: one fp32 multiply    */
+/* per element, the tables as they stand); gu[:, :q_dim], gu[:, q_dim:]       */
+/* (concat).  An id whose q is out of range gets index -1 and zero rows in    */
+/* both slices; so do the entries past min(n, *n_dev).  For DR_MHV_ADD r_val  */
+/* may equal q_val (one block serves both slices).                            */
+int dr_mhv_grad(const float* q_table, int64_t q_rows, int q_dim, const float* r_table,
+                int64_t r_rows, int r_dim, int operation, const int64_t* uniq, const float* gu,
+                int64_t n, const int64_t* n_dev, int64_t* q_idx, int64_t* r_idx, float* q_val,
+                float* r_val, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Checkpoint support (host function, no device work): crc32c::Extend of    */
 /* core/lib/hash/crc32c.h, used for TensorBundle entry and SSTable block     */
 /* checksums (core/util/tensor_bundle/tensor_bundle.cc:435-455).             */
