@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "dr_common.h"
+#include "dr_opt_elem.h"
 #include "dr_rows.h"
 
 namespace dr {
@@ -701,113 +702,12 @@ struct ApplyCols {
   int32_t trows0;
 };
 
-enum {
-  OPT_SGD = 0,
-  OPT_ADAGRAD = 1,
-  OPT_ADAM = 2,
-  OPT_FTRL = 3,
-  OPT_ADAM_ASYNC = 4,     // KvSparseApplyAdamAsync (training_ali_ops.cc:1404-1575)
-  OPT_ADAM_RMSPROP = 5,   //   ... with apply_sparse_rmsprop (:1483-1519)
-  OPT_ADAGRAD_DECAY = 6   // KvSparseApplyAdagradDecay (training_ali_ops.cc:703-823)
-};
-// var + two slot columns (m / v, or accum / accum_decay_power)
-__host__ __device__ constexpr bool opt_three_cols(int opt) {
-  return opt == OPT_ADAM || opt == OPT_ADAM_ASYNC || opt == OPT_ADAM_RMSPROP ||
-         opt == OPT_ADAGRAD_DECAY;
-}
-
-struct OptScalars {
-  float lr, beta1, beta2, eps, alpha;
-  float l1, l2, lr_power, l2_shrinkage;  // FTRL
-  float decay_rate, decay_baseline;      // AdagradDecay
-  int64_t decay_step;
-};
-
 // Two phases per wave of 64 keys.  Phase 1, lane per key: LookupOrCreate
 // with the global step / filter admission / first-touch column mask (the
 // dependent hash probes of 64 keys overlap).  Phase 2: groups of G lanes
 // update 64/G rows at a time with VEC-wide loads/stores; every element is
-// the reference's scalar formula with separate fp32 roundings.
-template <int OPT, int VEC, int G>
-__device__ __forceinline__ float apply_one(float gv, float w, float* a1, float* a2,
-                                           const OptScalars& sc) {
-  if (OPT == OPT_SGD) {
-    const float p = sc.lr * gv;  // v -= lr * g  (training_ali_ops.cc:1663)
-    return w - p;
-  } else if (OPT == OPT_ADAGRAD) {  // training_ali_ops.cc:131-132
-    float a = *a1;
-    const float g2 = gv * gv;
-    a = a + g2;
-    const float lg_ = sc.lr * gv;
-    const float rs = 1.0f / sqrtf(a);
-    const float up = lg_ * rs;
-    *a1 = a;
-    return w - up;
-  } else if (OPT == OPT_ADAM_ASYNC) {  // training_ali_ops.cc:1552-1554
-    float m = *a1;
-    float v = *a2;
-    const float mt = m * sc.beta1;
-    const float mg = gv * (1.0f - sc.beta1);
-    m = mt + mg;
-    const float vt = v * sc.beta2;
-    const float g2 = gv * gv;
-    const float vg = g2 * (1.0f - sc.beta2);
-    v = vt + vg;
-    const float num = m * sc.alpha;
-    const float den = sqrtf(v) + sc.eps;
-    *a1 = m;
-    *a2 = v;
-    return w - num / den;
-  } else if (OPT == OPT_ADAM_RMSPROP) {  // training_ali_ops.cc:1506-1513
-    float m = *a1;
-    float v = *a2;
-    const float vt = v * sc.beta2;
-    const float g2 = gv * gv;
-    const float vg = g2 * (1.0f - sc.beta2);
-    v = vt + vg;
-    const float rs = 1.0f / sqrtf(v + sc.eps);
-    const float step = (rs * sc.lr) * gv;
-    const float mt = m * sc.beta1;
-    m = mt + step;
-    *a1 = m;
-    *a2 = v;
-    return w - m;
-  } else {  // OPT_ADAM, training_ali_ops.cc:952-958
-    float m = *a1;
-    float v = *a2;
-    float t1 = gv - m;
-    t1 = t1 * (1.0f - sc.beta1);
-    m = m + t1;
-    float t2 = gv * gv;
-    t2 = t2 - v;
-    t2 = t2 * (1.0f - sc.beta2);
-    v = v + t2;
-    const float num = m * sc.alpha;
-    const float den = sqrtf(v) + sc.eps;
-    *a1 = m;
-    *a2 = v;
-    return w - num / den;
-  }
-}
-
-// AdagradDecay element (training_ali_ops.cc:802-808): when the row decays
-// this step, a = max(a * rate, baseline) (cwiseMax: a < b ? b : a), then
-// a += g^2; v -= (lr * g) * rsqrt(a).
-__device__ __forceinline__ float adagrad_decay_one(float gv, float w, float* a1, bool dec,
-                                                   const OptScalars& sc) {
-  float a = *a1;
-  if (dec) {
-    a = a * sc.decay_rate;
-    a = a < sc.decay_baseline ? sc.decay_baseline : a;
-  }
-  const float g2 = gv * gv;
-  a = a + g2;
-  const float lg_ = sc.lr * gv;
-  const float rs = 1.0f / sqrtf(a);
-  const float up = lg_ * rs;
-  *a1 = a;
-  return w - up;
-}
+// the reference's scalar formula with separate fp32 roundings
+// (apply_one / adagrad_decay_one, dr_opt_elem.h).
 
 // One table of a grouped apply launch (blockIdx.y selects it).
 struct ApplyTable {

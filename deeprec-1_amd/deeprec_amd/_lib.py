@@ -93,6 +93,15 @@ class DrMhvDesc(C.Structure):
     ]
 
 
+class DrDenseApplyDesc(C.Structure):
+    """dr_dense_apply_desc (include/deeprec_amd.h): one dense table's sparse apply."""
+    _fields_ = [
+        ("table", C.c_void_p), ("rows", C.c_int64), ("dim", C.c_int32), ("slot1", C.c_void_p),
+        ("slot2", C.c_void_p), ("powers", C.c_void_p), ("grad", C.c_void_p), ("idx", C.c_void_p),
+        ("n", C.c_int64), ("n_dev", C.c_void_p),
+    ]
+
+
 class DrEvConfig(C.Structure):
     _fields_ = [
         ("dim", C.c_int64), ("capacity", C.c_int64), ("steps_to_live", C.c_int64),
@@ -423,6 +432,8 @@ SIGNATURES = {
     "dr_mhv_gather": (_I32, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P]),
     "dr_mhv_grad": (_I32, [_P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P, _P,
                            _P]),
+    "dr_dense_apply_grouped_workspace_size": (_SZ, [_P, _I32]),
+    "dr_dense_apply_grouped": (_I32, [_I32, _P, _I32, _F32, _F32, _F32, _F32, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -79,6 +79,12 @@ def _rounds(slices):
 # SGD applies of row-grouped backwards use the forward's rows (A/B switch)
 _KNOWN_ROWS = os.environ.get("DR_APPLY_PROBE") != "1"
 
+# Dense tables of SGD / Adagrad / AdamAsync are applied by the grouped HIP
+# apply (dr_dense_apply_grouped: dedup and update on the device, the count
+# read there, capturable).  A/B switch DR_DENSE_APPLY=torch: unique +
+# unsorted_segment_sum + torch indexing (_apply_dense), one host read per table
+_NATIVE_DENSE = os.environ.get("DR_DENSE_APPLY", "native") != "torch"
+
 # KV Adam with its beta powers in HBM (A/B switch DR_KV_ADAM_DEVICE_POWERS=0)
 _ADAM_DEVICE_POWERS = os.environ.get("DR_KV_ADAM_DEVICE_POWERS", "1") != "0"
 
@@ -116,8 +122,39 @@ class _Locked(object):
         return False
 
 
+def _dense_slice(pending, count_gate):
+    """(values [n, D], indices [n], n_dev) of a dense table's pending slices
+    for dr_dense_apply_grouped, without a host read.  One slice passes as is.
+    Several are concatenated at full capacity, the tail of each set to -1 (a
+    skipped index) by a device-side compare against its num_valid; with
+    count_gate the device count is the capacity when any slice holds a row
+    and 0 when none does (AdamAsync's `if (N > 0)`)."""
+    if len(pending) == 1:
+        sl = pending[0]
+        return (sl.values.to(torch.float32).contiguous(),
+                sl.indices.to(torch.int64).contiguous(), sl.num_valid)
+    vals, idxs, held = [], [], None
+    for sl in pending:
+        i = sl.indices.to(torch.int64)
+        if sl.num_valid is not None:
+            nv = sl.num_valid.reshape(-1)[:1].to(torch.int64)
+            i = torch.where(torch.arange(i.numel(), device=i.device) < nv, i,
+                            torch.full_like(i, -1))
+            if count_gate:
+                nv = nv.clamp(0, i.numel())
+                held = nv if held is None else held + nv
+        vals.append(sl.values.to(torch.float32))
+        idxs.append(i)
+    v, i = torch.cat(vals).contiguous(), torch.cat(idxs).contiguous()
+    n_dev = None
+    if held is not None and all(sl.num_valid is not None for sl in pending):
+        n_dev = torch.where(held > 0, torch.full_like(held, i.numel()), torch.zeros_like(held))
+    return v, i, n_dev
+
+
 class _Optimizer(object):
     _opt = None   # DR_OPT_* code of the EV apply kernel
+    _dense_opt = None   # DR_OPT_* code of dr_dense_apply_grouped (None: torch path only)
 
     def __init__(self, learning_rate, use_locking=False):
         self.lr = float(learning_rate)
@@ -137,6 +174,7 @@ class _Optimizer(object):
         if self._opt == 0 and _KNOWN_ROWS:
             self._apply_fused_rows(var_list, gs)
         rounds = []   # rounds[r] = [(var, slices)] applied in one grouped launch
+        dense = []    # [(DenseTable, pending slices)] of the grouped native apply
         for var in var_list:
             if not var.pending_grads:
                 continue
@@ -150,11 +188,16 @@ class _Optimizer(object):
                         rounds.append([])
                     rounds[r].append((var, sl))
             elif isinstance(var, DenseTable):
-                self._apply_dense(var, _dedup(pending))
+                if self._dense_native(var):
+                    dense.append((var, pending))
+                else:
+                    self._apply_dense(var, _dedup(pending))
             else:
                 raise TypeError("unsupported variable %r" % (var,))
         for items in rounds:
             self._apply_ev_batch(items, gs)
+        if dense:
+            self._apply_dense_grouped(dense)
         if late:
             _mark_updated_hbm(*late)
         self._finish()
@@ -298,11 +341,58 @@ class _Optimizer(object):
         n = sl.indices.numel() if sl.num_valid is None else int(sl.num_valid.item())
         self._dense_update(var, sl.indices[:n], sl.values[:n])
 
+    def _dense_native(self, var):
+        """The table takes dr_dense_apply_grouped: one of its optimizers, fp32
+        rows on a GPU, a row width it has a shape for."""
+        w = var.weight
+        return (_NATIVE_DENSE and self._dense_opt is not None and w.is_cuda
+                and w.dtype == torch.float32 and w.is_contiguous()
+                and (w.shape[1] <= 256
+                     or (w.shape[1] % 4 == 0 and w.shape[1] <= 1024 and w.data_ptr() % 16 == 0)))
+
+    def _dense_slots(self, var):
+        """(slot1, slot2, powers) of a dense table, created on first use where
+        the torch path keeps them (the two paths share their state)."""
+        return None, None, None
+
+    def _dense_scalars(self):
+        return 0.0, 0.0, 0.0   # beta1, beta2, epsilon
+
+    def _apply_dense_grouped(self, items):
+        """One dr_dense_apply_grouped per device over every dense table with
+        pending gradients: nothing is read back, so the step can be captured."""
+        import ctypes as C
+        from ._lib import DrDenseApplyDesc, workspace
+        groups = {}
+        for var, pending in items:
+            groups.setdefault(str(var.weight.device), []).append((var, pending))
+        b1, b2, eps = self._dense_scalars()
+        for grp in groups.values():
+            dev = grp[0][0].weight.device
+            descs = (DrDenseApplyDesc * len(grp))()
+            keep = []
+            for d, (var, pending) in zip(descs, grp):
+                v, i, n_dev = _dense_slice(pending, self._dense_opt == 3)
+                if v.data_ptr() % 16 and var.dim > 256:
+                    v = v.clone()
+                s1, s2, pw = self._dense_slots(var)
+                keep.append((v, i, n_dev))
+                d.table, d.rows, d.dim = var.weight.data_ptr(), var.weight.shape[0], var.dim
+                d.slot1, d.slot2, d.powers = ptr(s1), ptr(s2), ptr(pw)
+                d.grad, d.idx, d.n, d.n_dev = v.data_ptr(), i.data_ptr(), i.numel(), ptr(n_dev)
+            with torch.cuda.device(dev):
+                wsb = lib().dr_dense_apply_grouped_workspace_size(descs, len(grp))
+                ws = workspace(wsb, dev)
+                check(lib().dr_dense_apply_grouped(self._dense_opt, descs, len(grp), self.lr, b1,
+                                                   b2, eps, ptr(ws), wsb, stream_handle(dev)))
+            ops._post(dev)
+
 
 class GradientDescentOptimizer(_Optimizer):
     """KvResourceSparseApplyGradientDescent (training_ali_ops.cc:1597-1678)."""
 
     _opt = 0
+    _dense_opt = 0
     _ev_duplicates = "sequential"
 
     def _dense_update(self, var, idx, g):
@@ -313,11 +403,18 @@ class AdagradOptimizer(_Optimizer):
     """KvSparseApplyAdagrad (training_ali_ops.cc:61-145)."""
 
     _opt = 1
+    _dense_opt = 1
 
     def __init__(self, learning_rate, initial_accumulator_value=0.1, use_locking=False):
         super().__init__(learning_rate, use_locking)
         self.init_acc = float(initial_accumulator_value)
         self._dense_acc = {}
+
+    def _dense_slots(self, var):
+        acc = self._dense_acc.get(id(var))
+        if acc is None:
+            acc = self._dense_acc[id(var)] = torch.full_like(var.weight, self.init_acc)
+        return acc, None, None
 
     def _slots(self, var):
         return var.slot("Adagrad", self.init_acc), None
@@ -561,6 +658,7 @@ class AdamAsyncOptimizer(_Optimizer):
         self.beta1, self.beta2, self.eps = float(beta1), float(beta2), float(epsilon)
         self.apply_sparse_rmsprop = bool(apply_sparse_rmsprop)
         self._opt = 4 if self.apply_sparse_rmsprop else 3
+        self._dense_opt = self._opt   # DR_OPT_ADAM_ASYNC[_RMSPROP]
         self._powers = {}     # id(var) -> device float32[2] {beta1_power, beta2_power}
         self._dense_mv = {}
 
@@ -581,6 +679,16 @@ class AdamAsyncOptimizer(_Optimizer):
     def _power(self, var):
         """(beta1_power, beta2_power) as host floats (reads the device)."""
         return self._power_t(var).tolist()
+
+    def _dense_scalars(self):
+        return self.beta1, self.beta2, self.eps
+
+    def _dense_slots(self, var):
+        mv = self._dense_mv.get(id(var))
+        if mv is None:
+            mv = self._dense_mv[id(var)] = (torch.zeros_like(var.weight),
+                                            torch.zeros_like(var.weight))
+        return mv[0], mv[1], None if self.apply_sparse_rmsprop else self._power_t(var)
 
     def _apply_ev_batch(self, items, gs):
         import ctypes as C

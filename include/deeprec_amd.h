@@ -1843,6 +1843,62 @@ int dr_mhv_grad(const float* q_table, int64_t q_rows, int q_dim, const float* r_
                 float* r_val, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Grouped sparse apply for dense tables (hash-bucket columns' tables, both  */
+/* tables of a MultiHashVariable): the optimizer's                           */
+/* _deduplicate_indexed_slices (python/training/optimizer.py:68-83: unique + */
+/* unsorted_segment_sum) and the row update of ResourceSparseApply*, on the  */
+/* device with the gradient's DEVICE row count.  Table t, with N = min(n,    */
+/* *n_dev) (N = n when n_dev is NULL):                                       */
+/*  - for every distinct row r named by idx[0..N) with 0 <= r < rows the     */
+/*    gradient is gsum = 0.0f + g[i0] + g[i1] + ..., ONE serial fp32 chain   */
+/*    over the positions naming r in ascending order (UnsortedSegmentSum     */
+/*    order: what dr_unique + dr_unsorted_segment_sum return; no float       */
+/*    atomics), and the optimizer's element update is applied once to row r; */
+/*  - idx < 0 is skipped silently (dr_mhv_grad's -1); idx >= rows inside the */
+/*    count is skipped and latches DR_INVALID_ARGUMENT (dr_status_check), as */
+/*    dr_gather does; nothing at or past position N is read as a row id, so  */
+/*    entries past the count may hold anything;                              */
+/*  - N == 0 changes nothing, the beta powers included.                      */
+/* optimizer: DR_OPT_SGD; DR_OPT_ADAGRAD (slot1 = accumulator);              */
+/* DR_OPT_ADAM_ASYNC and DR_OPT_ADAM_ASYNC_RMSPROP (slot1 = m, slot2 = v).   */
+/* The element updates are the EV applies' own (dr_ev_apply_grouped): a      */
+/* dense table and an EV holding the same rows take bit-identical steps.     */
+/* DR_OPT_ADAM_ASYNC forms alpha in the kernel from `powers` (device         */
+/* {beta1_power, beta2_power}, one pair per table) as they stand and, after  */
+/* the rows are done, multiplies them by beta1 / beta2 iff N > 0, as         */
+/* dr_ev_apply_adam_async_grouped does.  Any other optimizer code is         */
+/* DR_INVALID_ARGUMENT.                                                      */
+/* Any number of descriptors; dim may differ between them (up to 1024 when a */
+/* multiple of 4 with table, slots and grad 16-byte aligned, else up to 256).*/
+/* Every table runs the row shape of its own width and alignment: the        */
+/* descriptors are launched in groups of one row shape, DR_MAX_GROUP tables  */
+/* at a time, so what a table is accepted with never depends on the other    */
+/* tables of the call or on their order.  Two descriptors naming one table,  */
+/* an n or a launch group's total n that reaches 2^31, null required         */
+/* pointers, an unsupported width and a workspace below                      */
+/* dr_dense_apply_grouped_workspace_size() are DR_INVALID_ARGUMENT before    */
+/* any launch.  The entry does not allocate, synchronise or read back: it is */
+/* legal under stream capture.                                               */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  float* table;            /* [rows, dim] fp32, updated in place             */
+  int64_t rows;
+  int32_t dim;
+  float* slot1;            /* [rows, dim] fp32 or NULL (see optimizer)       */
+  float* slot2;
+  float* powers;           /* device float[2], DR_OPT_ADAM_ASYNC only        */
+  const float* grad;       /* [n, dim]                                       */
+  const int64_t* idx;      /* [n] row ids; may repeat; < 0 = skip            */
+  int64_t n;               /* capacity                                       */
+  const int64_t* n_dev;    /* optional DEVICE count                          */
+} dr_dense_apply_desc;
+size_t dr_dense_apply_grouped_workspace_size(const dr_dense_apply_desc* descs_host,
+                                             int num_tables);
+int dr_dense_apply_grouped(int optimizer, const dr_dense_apply_desc* descs_host, int num_tables,
+                           float lr, float beta1, float beta2, float epsilon, void* ws,
+                           size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Checkpoint support (host function, no device work): crc32c::Extend of    */
 /* core/lib/hash/crc32c.h, used for TensorBundle entry and SSTable block     */
 /* checksums (core/util/tensor_bundle/tensor_bundle.cc:435-455).             */
