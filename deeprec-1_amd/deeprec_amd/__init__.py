@@ -10,13 +10,16 @@ optimizers) on torch device tensors.
 from . import _lib
 from . import torch_ops  # noqa: F401  (registers torch.ops.deeprec.*)
 from ._lib import DeepRecError, InvalidArgumentError, load
-from .embedding_ops import (DenseTable, SparseTensor, embedding_lookup, embedding_lookup_sparse,
+from .embedding_ops import (DenseTable, SparseTensor, adaptive_embedding_lookup_sparse,
+                            embedding_lookup, embedding_lookup_sparse,
                             embedding_lookup_sparse_multi, fused_embedding_lookup_sparse,
                             safe_embedding_lookup_sparse)
-from .kv_variable_ops import (CBFFilter, CounterFilter, EmbeddingVariable, EmbeddingVariableOption,
+from .kv_variable_ops import (AdaptiveEmbeddingVariable, CBFFilter, CounterFilter,
+                              EmbeddingVariable, EmbeddingVariableOption,
                               GlobalStepEvict, IndexedSlices, InitializerOption, KeyBudgetEvict,
                               MultiHashVariable, MultiHashVariableConfig, StorageOption,
-                              StorageType, flush_releases, get_embedding_variable,
+                              StorageType, flush_releases, get_adaptive_embedding_variable,
+                              get_embedding_variable,
                               get_multihash_variable, read_only_lookups, read_only_serves_tier)
 from .ops import set_validate, status_check
 from .string_ops import StringTensor, string_to_hash_bucket_fast
@@ -33,5 +36,6 @@ __all__ = [
     "FtrlOptimizer", "GradientDescentOptimizer", "StringTensor",
     "string_to_hash_bucket_fast", "StorageOption", "StorageType", "InitializerOption",
     "read_only_serves_tier", "MultiHashVariable", "MultiHashVariableConfig",
-    "get_multihash_variable",
+    "get_multihash_variable", "AdaptiveEmbeddingVariable", "get_adaptive_embedding_variable",
+    "adaptive_embedding_lookup_sparse",
 ]

@@ -434,6 +434,11 @@ SIGNATURES = {
                            _P]),
     "dr_dense_apply_grouped_workspace_size": (_SZ, [_P, _I32]),
     "dr_dense_apply_grouped": (_I32, [_I32, _P, _I32, _F32, _F32, _F32, _F32, _P, _SZ, _P]),
+    "dr_adaptive_split_workspace_size": (_SZ, [_I64]),
+    "dr_adaptive_split": (_I32, [_P, _P, _I64, _P, _P, _I32, _P, _I64, _P, _I32, _P, _P, _P, _P, _P,
+                                 _P, _P, _P, _P, _SZ, _P]),
+    "dr_adaptive_merge": (_I32, [_P, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "dr_adaptive_grad": (_I32, [_P, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -17,9 +17,9 @@ import torch
 
 from . import _lib, ops
 from ._lib import COMBINERS, ORDER_ALI, ORDER_SEQ, DrPoolDesc, check, lib, ptr, stream_handle, workspace
-from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, MultiHashVariable,
-                               PendingRowSlices, _refuse_tier_capture, promote_grouped,
-                               read_only_active,
+from .kv_variable_ops import (AdaptiveEmbeddingVariable, EmbeddingVariable, IndexedSlices,
+                               MultiHashVariable, PendingRowSlices, _refuse_adaptive,
+                               _refuse_tier_capture, promote_grouped, read_only_active,
                                read_only_serves_tier, tier_hits, tier_serve_overlay)
 
 
@@ -89,9 +89,15 @@ class _Feature(object):
     seg: sorted segment ids -- an int32/int64 vector, or the [nnz, 2] int64
     sp_ids.indices (read in place, stride 2: no per-step conversion)."""
 
-    def __init__(self, params, values, seg, batch, weights, combiner, max_norm, onehot=False):
+    def __init__(self, params, values, seg, batch, weights, combiner, max_norm, onehot=False,
+                 mask=None, hash_ids=None):
         if isinstance(params, MultiHashVariable) and max_norm is not None:
             _refuse_mhv("max_norm (the reference clips each sub-lookup; not built)")
+        # adaptive features: the per-position mask (nonzero: the id lives in the
+        # EV) and, optionally, the already-hashed bucket rows
+        self.mask, self.hash_ids = _adaptive_inputs(params, values, max_norm, mask, hash_ids)
+        self.adaptive = None    # (mask_u, hrow, ev_keys, ev_src, Ue) after _prepare
+        self.frozen = False     # prepared inside read_only_lookups(): no gradient
         vd = getattr(params, "value_dtype", torch.float32)
         if vd != torch.float32 and not (vd == torch.bfloat16 and isinstance(params,
                                                                            EmbeddingVariable)):
@@ -146,6 +152,49 @@ class _Feature(object):
             s = self.seg64 if self.seg_stride == 1 else self.seg64[:, 0]
             self._seg32 = s.to(torch.int32).contiguous()
         return self._seg32
+
+
+def _adaptive_inputs(params, values, max_norm, mask, hash_ids):
+    """The mask and bucket rows of an adaptive feature as the kernels take them
+    (mask: uint8 / int32 / int64 [nnz]; hash rows: int64 [nnz] or None)."""
+    if not isinstance(params, AdaptiveEmbeddingVariable):
+        if mask is not None or hash_ids is not None:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "adaptive_mask_tensor / hash_ev_ids go with an "
+                "AdaptiveEmbeddingVariable; %s is none" % (getattr(params, "name", type(params)),))
+        return None, None
+    if max_norm is not None:
+        _refuse_adaptive("max_norm (not built)")
+    if mask is None:
+        _refuse_adaptive("a lookup without adaptive_mask_tensor (one entry per id: nonzero = "
+                         "the id lives in the EV)")
+    mask = torch.as_tensor(mask).reshape(-1)
+    if mask.is_floating_point() or mask.is_complex():
+        _refuse_adaptive("a %s adaptive_mask_tensor (integer or bool)" % (mask.dtype,))
+    n = values.numel()
+    if mask.numel() != n:
+        _refuse_adaptive("an adaptive_mask_tensor of %d entries for %d ids" % (mask.numel(), n))
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    elif mask.dtype not in (torch.uint8, torch.int32, torch.int64):
+        mask = mask.to(torch.int64)
+    if hash_ids is not None:
+        hash_ids = _hash_values(hash_ids)
+        hash_ids = torch.as_tensor(hash_ids).reshape(-1)
+        if hash_ids.numel() != n:
+            _refuse_adaptive("hash_ev_ids of %d entries for %d ids" % (hash_ids.numel(), n))
+        hash_ids = hash_ids.to(device=values.device, dtype=torch.int64).contiguous()
+    return mask.to(values.device).contiguous(), hash_ids
+
+
+def _hash_values(hash_ev_ids):
+    """hash_ev_ids: a SparseTensor with the indices of sp_ids, or its values."""
+    return hash_ev_ids.values if isinstance(hash_ev_ids, SparseTensor) else hash_ev_ids
+
+
+def _has_adaptive(params):
+    ps = params if isinstance(params, (list, tuple)) else [params]
+    return any(isinstance(p, AdaptiveEmbeddingVariable) for p in ps)
 
 
 def _refuse_mhv(what):
@@ -224,8 +273,59 @@ def _prepare(f, need_unique):
         f.defaults = p._defaults_for(f.uniq.numel(), None)
         # (_run / embedding_stack promoted the group's keys: no second probe per feature)
         f.rows = p._resolve(f.uniq, f.U, cnt, f.defaults)
+    elif isinstance(p, AdaptiveEmbeddingVariable):
+        _prepare_adaptive(f)
     elif need_unique:
         f.uniq, f.idx, _, f.U = ops.unique_device(f.values)
+
+
+def _prepare_adaptive(f):
+    """Unique -> dr_adaptive_split -> the EV's resolve over the compacted EV
+    keys, with the hash rows they have been training as their per-key defaults
+    (inside read_only_lookups(): its find, nothing is created) ->
+    dr_adaptive_merge: one row selection per unique id, >= 0 an EV pool row,
+    -(h + 1) row h of the hash table.  No count is read on the host."""
+    import ctypes as C
+    p = f.params
+    ev, table = p.ev, p.hash_table.weight
+    dev = f.values.device
+    read_only = read_only_active()
+    with_counts = ev.filter_freq != 0 and not read_only
+    f.uniq, f.idx, cnt, f.U = ops.unique_device(f.values, with_counts)
+    n = f.values.numel()
+    m = max(n, 1)
+    mask_u = torch.empty(m, dtype=torch.int32, device=dev)
+    hrow = torch.empty(m, dtype=torch.int64, device=dev)
+    ev_keys = torch.empty(m, dtype=torch.int64, device=dev)
+    ev_src = torch.empty(m, dtype=torch.int32, device=dev)
+    ev_cnt = torch.empty(m, dtype=torch.int32, device=dev) if with_counts else None
+    Ue = torch.empty(1, dtype=torch.int64, device=dev)
+    defaults = torch.empty((m, p.dim), dtype=torch.float32, device=dev)
+    rows_u = torch.empty(m, dtype=torch.int64, device=dev)
+    wsb = lib().dr_adaptive_split_workspace_size(n)
+    ws = workspace(wsb, dev)
+    st = stream_handle(dev)
+    check(lib().dr_adaptive_split(ptr(f.uniq), ptr(f.idx), n, ptr(f.U), ptr(f.mask),
+                                  f.mask.element_size(), ptr(f.hash_ids), p.bucket_size,
+                                  ptr(table), p.dim, ptr(cnt), ptr(mask_u), ptr(hrow),
+                                  ptr(ev_keys), ptr(ev_src), ptr(ev_cnt), ptr(Ue), ptr(defaults),
+                                  ptr(ws), wsb, st))
+    if n == 0:
+        ev_rows = rows_u
+    elif read_only:
+        ev_rows = torch.empty(m, dtype=torch.int64, device=dev)
+        check(lib().dr_ev_find_grouped((C.c_void_p * 1)(ev.handle.value), 1, ptr(ev_keys),
+                                       ops._koff_array([0, n]), (C.c_void_p * 1)(Ue.data_ptr()),
+                                       ptr(ev_rows), st))
+    else:
+        ev_rows = ev._resolve(ev_keys[:n], Ue, ev_cnt, defaults)
+    check(lib().dr_adaptive_merge(ptr(mask_u), ptr(hrow), ptr(ev_src), ptr(ev_rows), n, ptr(f.U),
+                                  ptr(Ue), ptr(rows_u), st))
+    ops._post(dev)
+    f.rows = rows_u
+    f.defaults = None
+    f.adaptive = (mask_u, hrow, ev_keys, ev_src, Ue)
+    f.frozen = read_only
 
 
 def _desc(f, out, out_stride):
@@ -242,6 +342,15 @@ def _desc(f, out, out_stride):
         else:
             d.default_rows = ptr(_ev_default_dev(p))
             d.default_stride = 0
+    elif isinstance(p, AdaptiveEmbeddingVariable):
+        # two row sources for the one pooling kernel: a selection >= 0 is a row
+        # of the EV's pool, -(h + 1) row h of the hash table
+        d.pool = p.ev.pool()
+        d.pool_rows = 0
+        d.idx = ptr(f.idx)
+        d.rows = ptr(f.rows)
+        d.default_rows = ptr(p.hash_table.weight)
+        d.default_stride = p.dim
     elif isinstance(p, EmbeddingVariable):
         d.pool = p.pool()
         d.pool_rows = 0
@@ -366,6 +475,10 @@ def _queue_grads(feats, g, col0, total, tensors=()):
         if isinstance(holder, MultiHashVariable):
             _mhv_queue(holder, _grad_to_slices(f, g, cols[i], total))
             continue
+        if isinstance(holder, AdaptiveEmbeddingVariable):
+            if not f.frozen:
+                _adaptive_queue(holder, f, _grad_to_slices(f, g, cols[i], total))
+            continue
         holder.pending_grads.append(_grad_to_slices(f, g, cols[i], total))
     return dense
 
@@ -397,6 +510,25 @@ def _mhv_queue(p, sl):
     ops._post(dev)
     p.val_list[0].pending_grads.append(IndexedSlices(qv, qi, sl.num_valid, False))
     p.val_list[1].pending_grads.append(IndexedSlices(rv, ri, sl.num_valid, False))
+
+
+def _adaptive_queue(p, f, sl):
+    """The per-unique-id gradient of an adaptive lookup -> the EV's slice (the
+    compacted EV keys with their gradient rows, dr_adaptive_grad; -1 is an
+    ordinary EV key, so nothing is padded) and the hash table's (bucket row or
+    -1 per unique id over gU itself: ids share buckets, the optimizer sums)."""
+    mask_u, hrow, ev_keys, ev_src, Ue = f.adaptive
+    gu = sl.values.contiguous()
+    n = f.values.numel()
+    dev = gu.device
+    ev_val = torch.empty((max(n, 1), p.dim), dtype=torch.float32, device=dev)
+    hidx = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    check(lib().dr_adaptive_grad(ptr(gu), p.dim, ptr(mask_u), ptr(hrow), ptr(ev_src), n,
+                                 ptr(sl.num_valid), ptr(Ue), ptr(ev_val), ptr(hidx),
+                                 stream_handle(dev)))
+    ops._post(dev)
+    p.ev.pending_grads.append(IndexedSlices(ev_val[:n], ev_keys[:n], Ue, True))
+    p.hash_table.pending_grads.append(IndexedSlices(gu[:n], hidx[:n], sl.num_valid, False))
 
 
 class _StackFn(torch.autograd.Function):
@@ -431,6 +563,9 @@ def embedding_stack(x0, params_list, sp_ids_list, combiner="sum"):
                                 "bf16 EVs: embedding_lookup_sparse_multi")
     if _has_mhv(list(params_list)):
         _refuse_mhv("embedding_stack (use embedding_lookup_sparse_multi)")
+    if _has_adaptive(list(params_list)):
+        _refuse_adaptive("embedding_stack (use embedding_lookup_sparse_multi with "
+                         "adaptive_masks)")
     feats = []
     for p, sp in zip(params_list, sp_ids_list):
         v = sp.values.to(torch.int64).contiguous()
@@ -1068,8 +1203,12 @@ def _run(feats, order=ORDER_ALI, need_grad=None, out_dtype=None, _plain=False):
     _promote_feats(feats)
     tensors =_trainable_tensors(feats) if torch.is_grad_enabled() else []
     if need_grad is None:
+        # (an adaptive feature inside read_only_lookups() carries no gradient)
+        ro = read_only_active()
         need_grad = torch.is_grad_enabled() and (
-            bool(tensors) or any(not torch.is_tensor(f.params) for f in feats))
+            bool(tensors) or any(not torch.is_tensor(f.params)
+                                 and not (ro and isinstance(f.params, AdaptiveEmbeddingVariable))
+                                 for f in feats))
     if not need_grad and _FUSED_ONEHOT:
         out = _fused_onehot(feats, order, out_dtype=out_dtype)
         if out is not None:
@@ -1168,12 +1307,20 @@ def _seg_of(sp_ids):
 
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy="mod", name=None,
-                            combiner=None, max_norm=None):
-    """tf.nn.embedding_lookup_sparse (embedding_ops.py:480-675), 2-D sp_ids."""
+                            combiner=None, max_norm=None, adaptive_mask_tensor=None,
+                            hash_ev_ids=None):
+    """tf.nn.embedding_lookup_sparse (embedding_ops.py:480-675), 2-D sp_ids.
+    An AdaptiveEmbeddingVariable takes adaptive_mask_tensor ([nnz], nonzero:
+    the id lives in the EV) and optionally hash_ev_ids (the bucket rows)."""
     if combiner is None:
         combiner = "mean"
     if combiner not in ("mean", "sqrtn", "sum", "tile"):
         raise ValueError("combiner must be one of 'mean', 'sqrtn', 'sum' or 'tile'")
+    if _has_adaptive(params):
+        if combiner == "tile":
+            _refuse_adaptive("combiner=\"tile\"")
+        if isinstance(params, (list, tuple)) and len(params) != 1:
+            _refuse_adaptive("a list of partitions: pass the variable itself")
     if _has_mhv(params):
         if combiner == "tile":
             _refuse_mhv("combiner=\"tile\"")
@@ -1192,29 +1339,76 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
     values = sp_ids.values.to(torch.int64).contiguous()
     w = None if sp_weights is None else sp_weights.values.to(torch.float32).contiguous()
     f = _Feature(params, values, _seg_of(sp_ids), sp_ids.dense_shape[0], w, combiner, max_norm,
-                 onehot=_is_onehot(sp_ids, values.numel()))
+                 onehot=_is_onehot(sp_ids, values.numel()), mask=adaptive_mask_tensor,
+                 hash_ids=hash_ev_ids)
     return _run([f])
 
 
+def adaptive_embedding_lookup_sparse(hash_params, ev_params, sp_ids, hash_ev_ids, sp_weights,
+                                     partition_strategy="mod", name=None, combiner=None,
+                                     max_norm=None, bucket_size=None, adaptive_mask_tensor=None):
+    """tf.nn.adaptive_embedding_lookup_sparse (embedding_ops.py), the
+    reference's argument order.  hash_params / ev_params: the two members of
+    one AdaptiveEmbeddingVariable, or the variable itself for either."""
+    var = None
+    for p in (hash_params, ev_params):
+        if isinstance(p, (list, tuple)):
+            if len(p) != 1:
+                _refuse_adaptive("a list of partitions: pass the variable or its two members")
+            p = p[0]
+        if isinstance(p, AdaptiveEmbeddingVariable):
+            if var is not None and var is not p:
+                _refuse_adaptive("two different variables as hash_params and ev_params")
+            var = p
+    if var is None:
+        hash_params, ev_params = [p[0] if isinstance(p, (list, tuple)) else p
+                                  for p in (hash_params, ev_params)]
+        if not (isinstance(hash_params, DenseTable) and isinstance(ev_params, EmbeddingVariable)):
+            _refuse_adaptive("hash_params / ev_params other than its hash table (DenseTable) "
+                             "and its EmbeddingVariable")
+        # (the variable is only a view of its two members: gradients queue on them)
+        var = AdaptiveEmbeddingVariable(ev_params.name, hash_params, ev_params)
+    if bucket_size is not None and int(bucket_size) != var.bucket_size:
+        _refuse_adaptive("bucket_size %d: its hash table has %d rows"
+                         % (int(bucket_size), var.bucket_size))
+    return embedding_lookup_sparse(var, sp_ids, sp_weights, partition_strategy, name, combiner,
+                                   max_norm, adaptive_mask_tensor=adaptive_mask_tensor,
+                                   hash_ev_ids=hash_ev_ids)
+
+
 def embedding_lookup_sparse_multi(params_list, sp_ids_list, combiner="mean", max_norm=None,
-                                  out_dtype=None):
+                                  out_dtype=None, adaptive_masks=None, hash_ev_ids_list=None):
     """Grouped lookup of several features (one pooled launch per 32 tables);
     returns the input_layer concatenation [B, sum(D_t)], fp32 -- or, for
     bf16 EVs with out_dtype=torch.bfloat16, bf16 (one-id bags copied
-    bitwise, longer bags pooled in fp32 and rounded once)."""
+    bitwise, longer bags pooled in fp32 and rounded once).  adaptive_masks /
+    hash_ev_ids_list: per feature, the mask (and bucket rows) of an
+    AdaptiveEmbeddingVariable, None for the other features."""
     feats = []
-    for p, sp in zip(params_list, sp_ids_list):
+    T = len(params_list)
+    masks = list(adaptive_masks) if adaptive_masks is not None else [None] * T
+    hashes = list(hash_ev_ids_list) if hash_ev_ids_list is not None else [None] * T
+    if len(masks) != T or len(hashes) != T:
+        raise ValueError("adaptive_masks / hash_ev_ids_list: one entry per feature (None for a "
+                         "feature that is not adaptive)")
+    for p, sp, mk, hs in zip(params_list, sp_ids_list, masks, hashes):
         v = sp.values.to(torch.int64)      # strided views stay views (_record_major)
         feats.append(_Feature(p, v, _seg_of(sp), sp.dense_shape[0], None, combiner, max_norm,
-                              onehot=_is_onehot(sp, v.numel())))
+                              onehot=_is_onehot(sp, v.numel()), mask=mk, hash_ids=hs))
     return _run(feats, out_dtype=out_dtype)
 
 
 def embedding_lookup(params, ids, partition_strategy="mod", name=None, max_norm=None,
-                     ev_init_value=None, counts=None):
+                     ev_init_value=None, counts=None, adaptive_mask_tensor=None, hash_ev_ids=None):
     """tf.nn.embedding_lookup (embedding_ops.py:94-342, 346)."""
     if isinstance(params, (list, tuple)) and len(params) == 1:
         params = params[0]
+    if _has_adaptive(params):
+        if isinstance(params, (list, tuple)):
+            _refuse_adaptive("a list of partitions: pass the variable itself")
+        return _adaptive_gather(params, ids, max_norm, adaptive_mask_tensor, hash_ev_ids)
+    if adaptive_mask_tensor is not None or hash_ev_ids is not None:
+        _adaptive_inputs(params, ids, max_norm, adaptive_mask_tensor, hash_ev_ids)
     if _has_mhv(params):
         if isinstance(params, (list, tuple)):
             raise TypeError("a MultiHashVariable is not partitioned: pass the variable itself, "
@@ -1242,6 +1436,19 @@ def embedding_lookup(params, ids, partition_strategy="mod", name=None, max_norm=
         r2 = r2 * max_norm / torch.maximum(l2, torch.tensor(max_norm, device=r2.device))
         res = r2.reshape(res.shape)
     return res
+
+
+def _adaptive_gather(p, ids, max_norm, mask, hash_ids):
+    """embedding_lookup over an AdaptiveEmbeddingVariable: the pooled lookup of
+    bags of one id (combiner sum), ids.shape + [dim] rows, with its gradient."""
+    flat = ids.reshape(-1).to(torch.int64).contiguous()
+    n = flat.numel()
+    seg = torch.arange(n, dtype=torch.int64, device=flat.device)
+    f = _Feature(p, flat, seg, n, None, "sum", max_norm, onehot=True, mask=mask,
+                 hash_ids=hash_ids)
+    if n == 0:
+        return torch.empty(tuple(ids.shape) + (p.dim,), dtype=torch.float32, device=flat.device)
+    return _run([f]).reshape(tuple(ids.shape) + (p.dim,))
 
 
 def _mhv_gather(p, ids, n_dev=None):
@@ -1495,14 +1702,67 @@ def _prune_and_fill(sp_ids, sp_weights, combiner, default_id, prune):
     return sp, spw, empty
 
 
+def _follow_prune_fill(x, n_in, rev, n_out):
+    """Per-position entries x [n_in] of the ids carried through
+    sparse_prune_fill: kept position k lands at rev[k]; a pruned position
+    (rev < 0) is dropped, a filled default id takes 0."""
+    x = torch.as_tensor(x).reshape(-1)
+    if x.numel() != n_in:
+        _refuse_adaptive("%d mask / hash entries for %d ids" % (x.numel(), n_in))
+    x = x.to(rev.device)
+    if x.dtype == torch.bool:
+        x = x.to(torch.uint8)
+    out = torch.zeros(n_out, dtype=x.dtype, device=rev.device)
+    keep = rev >= 0
+    out[rev[keep]] = x[keep]
+    return out
+
+
 def safe_embedding_lookup_sparse(embedding_weights, sparse_ids, sparse_weights=None,
                                  combiner="mean", default_id=None, name=None,
-                                 partition_strategy="div", max_norm=None, prune=True):
+                                 partition_strategy="div", max_norm=None, prune=True,
+                                 adaptive_mask_tensor=None, hash_ev_ids=None):
     if embedding_weights is None:
         raise ValueError("Missing embedding_weights %s." % embedding_weights)
+    if _has_adaptive(embedding_weights):
+        # mask and bucket rows follow their ids through the prune and the fill
+        if adaptive_mask_tensor is None:
+            _refuse_adaptive("a lookup without adaptive_mask_tensor (one entry per id: nonzero "
+                             "= the id lives in the EV)")
+        if max_norm is not None:
+            _refuse_adaptive("max_norm (not built)")
+        if combiner == "tile":
+            _refuse_adaptive("combiner=\"tile\"")
+        mode = 0 if not prune else (2 if sparse_weights is not None and combiner != "sum" else 1)
+        n_in = sparse_ids.values.numel()
+        for x in (adaptive_mask_tensor, _hash_values(hash_ev_ids)):
+            if x is not None and torch.as_tensor(x).numel() != n_in:
+                _refuse_adaptive("%d mask / hash entries for %d ids"
+                                 % (torch.as_tensor(x).numel(), n_in))
+        sp, spw, empty, rev = sparse_prune_fill(sparse_ids, sparse_weights, default_id, mode)
+        m = sp.values.numel()
+        mask = _follow_prune_fill(adaptive_mask_tensor, n_in, rev, m)
+        hs = None
+        if hash_ev_ids is not None:
+            hs = _follow_prune_fill(_hash_values(hash_ev_ids), n_in, rev,
+                                    m).to(torch.int64)
+            # a filled position has no supplied row: the bucket rule's
+            var = embedding_weights[0] if isinstance(embedding_weights, (list, tuple)) \
+                else embedding_weights
+            filled = torch.ones(m, dtype=torch.bool, device=hs.device)
+            filled[rev[rev >= 0]] = False
+            hs = torch.where(filled, torch.remainder(sp.values, var.bucket_size), hs)
+        res = embedding_lookup_sparse(embedding_weights, sp, spw,
+                                      partition_strategy=partition_strategy, combiner=combiner,
+                                      adaptive_mask_tensor=mask, hash_ev_ids=hs)
+        if default_id is None:
+            res = torch.where(empty[:, None], torch.zeros_like(res), res)
+        return res
     sp, spw, empty = _prune_and_fill(sparse_ids, sparse_weights, combiner, default_id, prune)
     res = embedding_lookup_sparse(embedding_weights, sp, spw, partition_strategy=partition_strategy,
-                                  combiner=combiner, max_norm=max_norm)
+                                  combiner=combiner, max_norm=max_norm,
+                                  adaptive_mask_tensor=adaptive_mask_tensor,
+                                  hash_ev_ids=hash_ev_ids)
     if default_id is None:
         res = torch.where(empty[:, None], torch.zeros_like(res), res)
     return res
@@ -1592,6 +1852,9 @@ def fused_embedding_lookup_sparse(embedding_weights, sparse_ids, combiner=None, 
         if isinstance(p, MultiHashVariable):
             raise TypeError("fused_embedding_lookup_sparse takes dense tables, not a "
                             "MultiHashVariable (embedding_lookup_sparse fuses its lookup)")
+        if isinstance(p, AdaptiveEmbeddingVariable):
+            _refuse_adaptive("fused_embedding_lookup_sparse (it takes dense tables; "
+                             "adaptive_embedding_lookup_sparse fuses the adaptive lookup)")
     tensors = [p for p in parts if torch.is_tensor(p) and p.requires_grad] \
         if torch.is_grad_enabled() else []
     anchors = [_anchor(p) for p in parts if isinstance(p, DenseTable)] \

@@ -1666,6 +1666,7 @@ def refuse_tiered_evs(evs, what):
     (the sharded engines): a tiered EV would be served defaults for the keys
     its host tier holds, so it is refused."""
     refuse_multihash(evs, what)
+    refuse_adaptive(evs, what)
     for ev in evs or ():    # (an engine built without local EVs has none to refuse)
         if getattr(ev, "tiered", False):
             raise _lib.InvalidArgumentError(
@@ -1812,3 +1813,92 @@ def get_multihash_variable(name, dims, complementary_strategy="Q-R", operation="
     tables = [_mhv_table("%s/%s" % (name, part), init, rows, dim, dev)
               for part, init, (rows, dim) in zip("QR", inits, cfg.size)]
     return MultiHashVariable(name, tables, cfg)
+
+
+# ---------------------------------------------------------------------------
+# AdaptiveEmbeddingVariable (variable_scope.py get_adaptive_embedding_variable,
+# embedding_ops.py adaptive_embedding_lookup_sparse): hot ids in an EV, cold
+# ids in a shared hash-bucket table
+# ---------------------------------------------------------------------------
+def _refuse_adaptive(what):
+    raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
+                                    "an AdaptiveEmbeddingVariable does not take " + what)
+
+
+class AdaptiveEmbeddingVariable(object):
+    """An EmbeddingVariable for the ids a mask names (private, collision-free
+    rows) over a small static hash-bucket table that all the other ids share:
+    id -> ev[id] where the mask is set, else hash_table[floormod(id,
+    bucket_size)] (csrc/dr_adaptive.h holds the rule).  An id that moves into
+    the EV starts from the hash row it has been training.  val_list =
+    [hash_table (DenseTable, fp32), ev (EmbeddingVariable, fp32)]; the lookups
+    of embedding_ops take the mask (adaptive_mask_tensor) and the backward
+    queues IndexedSlices on both members."""
+
+    def __init__(self, name, hash_table, ev):
+        if ev.value_dtype != torch.float32:
+            _refuse_adaptive("a %s EmbeddingVariable (%s): both members are float32"
+                             % (ev.value_dtype, ev.name))
+        if ev.tiered:
+            _refuse_adaptive("an HBM_DRAM EmbeddingVariable (%s): an id the host tier holds "
+                             "would be served its hash row" % ev.name)
+        if hash_table.weight.dtype != torch.float32:
+            _refuse_adaptive("a %s hash table" % (hash_table.weight.dtype,))
+        if hash_table.dim != ev.dim:
+            raise ValueError("AdaptiveEmbeddingVariable %s: hash table dim %d, EV dim %d"
+                             % (name, hash_table.dim, ev.dim))
+        if hash_table.device != ev.device:
+            raise ValueError("AdaptiveEmbeddingVariable %s: both members must be on one device"
+                             % name)
+        self.name = name
+        self.hash_table = hash_table
+        self.ev = ev
+        self.dim = ev.dim
+        self.device = ev.device
+        self.bucket_size = int(hash_table.weight.shape[0])
+
+    @property
+    def val_list(self):
+        return [self.hash_table, self.ev]
+
+    def get_shape(self):
+        return self.ev.get_shape()
+
+
+def get_adaptive_embedding_variable(name, embedding_dim, bucket_size, initializer=None,
+                                    ev_option=None, key_dtype=torch.int64, device=None):
+    """tf.get_adaptive_embedding_variable (variable_scope.py) without
+    partitioners: the hash table `name/hash` [bucket_size, embedding_dim] (the
+    initializer: a callable given the shape, a tensor taken as is, or a
+    scalar; default 0) and the EV `name/ev` made by get_embedding_variable with
+    ev_option (filters, GlobalStepEvict and init_option as for any EV; its
+    keys' initial rows come from the hash table, not from an initializer)."""
+    if name in _EV_REGISTRY:
+        return _EV_REGISTRY[name]
+    bucket_size = int(bucket_size)
+    if bucket_size < 1:
+        raise ValueError("bucket_size must be >= 1")
+    so = getattr(ev_option, "storage_option", None)
+    if so is not None and so.storage_type == StorageType.HBM_DRAM:
+        _refuse_adaptive("an HBM_DRAM EmbeddingVariable (%s): an id the host tier holds would be "
+                         "served its hash row" % name)
+    dev = torch.device(device) if device is not None else \
+        torch.device("cuda", torch.cuda.current_device())
+    table = _mhv_table("%s/hash" % name, initializer, bucket_size, int(embedding_dim), dev)
+    ev = get_embedding_variable("%s/ev" % name, embedding_dim, key_dtype=key_dtype,
+                                ev_option=ev_option, device=dev)
+    var = AdaptiveEmbeddingVariable(name, table, ev)
+    _EV_REGISTRY[name] = var
+    return var
+
+
+def refuse_adaptive(evs, what):
+    """The sharded engines shard EmbeddingVariables by key; an
+    AdaptiveEmbeddingVariable's lookup needs its mask and both its members on
+    one device."""
+    for ev in evs or ():
+        if isinstance(ev, AdaptiveEmbeddingVariable):
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "%s shards EmbeddingVariables; %s is an "
+                "AdaptiveEmbeddingVariable (look it up locally with "
+                "adaptive_embedding_lookup_sparse)" % (what, ev.name))

@@ -47,7 +47,7 @@ import torch.distributed as dist
 
 from . import _lib, ops
 from ._lib import COMBINERS, ORDER_ALI, DrPoolDesc, check, lib, ptr, stream_handle, workspace
-from .kv_variable_ops import refuse_multihash, refuse_tiered_evs
+from .kv_variable_ops import refuse_adaptive, refuse_multihash, refuse_tiered_evs
 
 
 class HipLocal(object):
@@ -917,6 +917,7 @@ class XgmiShardedLookup(object):
         if world > _lib.MAX_PEERS:
             raise ValueError("world %d > %d" % (world, _lib.MAX_PEERS))
         refuse_multihash(evs, "XgmiShardedLookup")
+        refuse_adaptive(evs, "XgmiShardedLookup")
         for e in evs:
             if e.filter_freq != 0:
                 raise ValueError("XgmiShardedLookup needs filter-free EVs")

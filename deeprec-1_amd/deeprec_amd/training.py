@@ -14,18 +14,22 @@ import torch
 from . import ops
 from ._lib import check, lib, ptr, stream_handle
 from .embedding_ops import DenseTable
-from .kv_variable_ops import (EmbeddingVariable, IndexedSlices, MultiHashVariable,
-                              PendingRowSlices, _flush_deferred_releases, _mark_updated_hbm,
-                              mark_updated_rows_grouped)
+from .kv_variable_ops import (AdaptiveEmbeddingVariable, EmbeddingVariable, IndexedSlices,
+                              MultiHashVariable, PendingRowSlices, _flush_deferred_releases,
+                              _mark_updated_hbm, mark_updated_rows_grouped)
+
+
+_COMPOSITE = (MultiHashVariable, AdaptiveEmbeddingVariable)
 
 
 def _expand_multihash(var_list):
-    """A MultiHashVariable in var_list stands for its two tables (each once)."""
-    if not any(isinstance(var, MultiHashVariable) for var in var_list):
+    """A MultiHashVariable in var_list stands for its two tables, an
+    AdaptiveEmbeddingVariable for its hash table and its EV (each once)."""
+    if not any(isinstance(var, _COMPOSITE) for var in var_list):
         return var_list
     out = []
     for var in var_list:
-        for v in (var.val_list if isinstance(var, MultiHashVariable) else [var]):
+        for v in (var.val_list if isinstance(var, _COMPOSITE) else [var]):
             if all(v is not o for o in out):
                 out.append(v)
     return out
@@ -339,7 +343,11 @@ class _Optimizer(object):
 
     def _apply_dense(self, var, sl):
         n = sl.indices.numel() if sl.num_valid is None else int(sl.num_valid.item())
-        self._dense_update(var, sl.indices[:n], sl.values[:n])
+        idx, val = sl.indices[:n], sl.values[:n]
+        keep = idx >= 0     # a negative index is skipped, as dr_dense_apply_grouped does
+        if not bool(keep.all()):
+            idx, val = idx[keep], val[keep]
+        self._dense_update(var, idx, val)
 
     def _dense_native(self, var):
         """The table takes dr_dense_apply_grouped: one of its optimizers, fp32

@@ -1899,6 +1899,57 @@ int dr_dense_apply_grouped(int optimizer, const dr_dense_apply_desc* descs_host,
                            size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Adaptive embedding (AdaptiveEmbeddingVariable): an id whose mask is set   */
+/* has a private row in an EV, every other id trains row h of a shared fp32  */
+/* hash-bucket table [bucket_size, dim]; an id that moves into the EV starts */
+/* from the hash row it has been training.  The three entries sit between    */
+/* dr_unique, dr_ev_resolve / dr_ev_find_grouped and dr_pool_grouped[_ex].   */
+/* Mask and bucket row are functions of the id: the id's first position      */
+/* (smallest k with idx[k] == u) decides.  n / nnz is the capacity of the    */
+/* per-unique arrays (dr_unique's), num_unique and num_ev DEVICE counts.     */
+/* None of the entries allocates, synchronises or reads anything back.  Null */
+/* or inconsistent arguments, a row width outside the shapes of              */
+/* dr_pool_grouped (up to 1024 floats when a multiple of 4 and the row       */
+/* blocks 16-byte aligned, else up to 256) and a short workspace are         */
+/* DR_INVALID_ARGUMENT before any launch.                                    */
+/* ------------------------------------------------------------------------ */
+/* Split.  For unique u < *num_unique, with f = first position of u:         */
+/*   mask_u[u] = mask[f] != 0 (mask: [nnz] of mask_bytes = 1, 4 or 8 bytes), */
+/*   hrow[u]   = hash ? hash[f] : floormod(uniq[u], bucket_size) (int64      */
+/*               floor semantics, csrc/dr_adaptive.h); a supplied row        */
+/*               outside [0, bucket_size) latches DR_INVALID_ARGUMENT        */
+/*               (dr_status_check) and becomes row 0.                        */
+/* The uniques with mask_u != 0, in ascending u (a stable compaction), are   */
+/* the EV keys: for j < *num_ev, ev_keys[j] = uniq[u], ev_src[j] = u,        */
+/* ev_counts[j] = counts[u] (both NULL, or both given) and defaults[j] =     */
+/* hash_table[hrow[u]] -- the per-key default block of dr_ev_resolve.        */
+/* Nothing at or past the counts is read or written as a row.                */
+size_t dr_adaptive_split_workspace_size(int64_t nnz);
+int dr_adaptive_split(const int64_t* uniq, const int32_t* idx, int64_t nnz,
+                      const int64_t* num_unique, const void* mask, int mask_bytes,
+                      const int64_t* hash /* nullable */, int64_t bucket_size,
+                      const float* hash_table, int dim, const int32_t* counts /* nullable */,
+                      int32_t* mask_u, int64_t* hrow, int64_t* ev_keys, int32_t* ev_src,
+                      int32_t* ev_counts /* nullable */, int64_t* num_ev, float* defaults,
+                      void* ws, size_t ws_bytes, void* stream);
+/* Merge.  ev_rows[j], j < *num_ev: the resolve (or find) of ev_keys, a      */
+/* negative value meaning "serve the default".  rows_u[u], u < *num_unique:  */
+/* the EV pool row of an EV id whose resolve gave one, else -(hrow[u] + 1):  */
+/* with dr_pool_desc.rows = rows_u, default_rows = the hash table and        */
+/* default_stride = dim the existing pooling serves both sources.            */
+int dr_adaptive_merge(const int32_t* mask_u, const int64_t* hrow, const int32_t* ev_src,
+                      const int64_t* ev_rows, int64_t n, const int64_t* num_unique,
+                      const int64_t* num_ev, int64_t* rows_u, void* stream);
+/* Gradient split of the per-unique gradient gu [n, dim]: ev_val[j] =         */
+/* gu[ev_src[j]] for j < *num_ev (rows past it are left as they are), and    */
+/* hash_idx[u] = hrow[u] where mask_u[u] == 0, -1 elsewhere and for every    */
+/* u >= *num_unique (dr_dense_apply_grouped skips a negative index; gu       */
+/* itself is the hash slice's value block).                                  */
+int dr_adaptive_grad(const float* gu, int dim, const int32_t* mask_u, const int64_t* hrow,
+                     const int32_t* ev_src, int64_t n, const int64_t* num_unique,
+                     const int64_t* num_ev, float* ev_val, int64_t* hash_idx, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Checkpoint support (host function, no device work): crc32c::Extend of    */
 /* core/lib/hash/crc32c.h, used for TensorBundle entry and SSTable block     */
 /* checksums (core/util/tensor_bundle/tensor_bundle.cc:435-455).             */
