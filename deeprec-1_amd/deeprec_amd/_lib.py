@@ -102,6 +102,18 @@ class DrDenseApplyDesc(C.Structure):
     ]
 
 
+DENSE_MAX_COLS = 4
+
+
+class DrDenseMarkDesc(C.Structure):
+    """dr_dense_mark_desc (include/deeprec_amd.h): one index vector marked on a
+    dense table's update bits."""
+    _fields_ = [
+        ("bits", C.c_void_p), ("rows", C.c_int64), ("idx", C.c_void_p), ("n", C.c_int64),
+        ("n_dev", C.c_void_p),
+    ]
+
+
 class DrEvConfig(C.Structure):
     _fields_ = [
         ("dim", C.c_int64), ("capacity", C.c_int64), ("steps_to_live", C.c_int64),
@@ -434,6 +446,14 @@ SIGNATURES = {
                            _P]),
     "dr_dense_apply_grouped_workspace_size": (_SZ, [_P, _I32]),
     "dr_dense_apply_grouped": (_I32, [_I32, _P, _I32, _F32, _F32, _F32, _F32, _P, _SZ, _P]),
+    "dr_dense_bits_num_words": (_I64, [_I64]),
+    "dr_dense_mark_rows": (_I32, [_P, _I32, _P]),
+    "dr_dense_mark_all": (_I32, [_P, _I64, _P]),
+    "dr_dense_clear_marks": (_I32, [_P, _I64, _P]),
+    "dr_dense_marked_count": (_I32, [_P, _I64, _P, _P]),
+    "dr_dense_export_marked_workspace_size": (_SZ, [_I64]),
+    "dr_dense_export_marked": (_I32, [_P, _I64, _I32, _P, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "dr_dense_upsert_rows": (_I32, [_P, _I32, _I64, _I32, _P, _I64, _P, _P, _P]),
     "dr_adaptive_split_workspace_size": (_SZ, [_I64]),
     "dr_adaptive_split": (_I32, [_P, _P, _I64, _P, _P, _I32, _P, _I64, _P, _I32, _P, _P, _P, _P, _P,
                                  _P, _P, _P, _P, _SZ, _P]),

@@ -33,6 +33,12 @@ dr_rows_pack, GPU) and `import_partitioned()` (dr_ev_insert, GPU).  Only the
 file bytes pass through the host; checksums run natively (dr_crc32c_extend).
 Values keep the EV's dtype on disk: DT_FLOAT, DT_DOUBLE, or DT_BFLOAT16 for a
 bf16 EV (build-defined, like the bf16 EV itself).
+
+Beside EVs the four entry points take DenseTables (one whole entry per table,
+as a tf.Variable is written; NAME-sparse_incr_{keys, values} in a delta),
+MultiHashVariables and AdaptiveEmbeddingVariables (their members,
+expand_variables) and the objects of optimizer.checkpoint_variables: slot
+EVs, dense slots and the beta-power scalars.
 """
 import os
 import struct
@@ -347,7 +353,7 @@ class BundleWriter(object):
             array = array.detach().cpu().numpy()
             if code:
                 array = array.view(np.uint16)
-        a = np.ascontiguousarray(array)
+        a = np.require(array, requirements="C")     # (keeps a rank-0 array rank 0)
         if a.dtype not in _DT:
             raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, "unsupported dtype %s" % a.dtype)
         a = a.astype(a.dtype.newbyteorder("<"), copy=False)
@@ -487,8 +493,95 @@ def write_ev_tensors(writer, tensor_key, offs, keys, vals, vers, frqs, suffix=""
     writer.add(pre + "freqs", frqs)
 
 
+# -- what a checkpoint call accepts beside EVs ---------------------------------
+def _kinds():
+    from .embedding_ops import DenseSlot, DenseTable, ScalarState
+    from .kv_variable_ops import (AdaptiveEmbeddingVariable, EmbeddingVariable,
+                                  MultiHashVariable)
+    return (EmbeddingVariable, (DenseTable, DenseSlot), ScalarState, MultiHashVariable,
+            AdaptiveEmbeddingVariable)
+
+
+def expand_variables(variables):
+    """{tensor_key: object} with the composites replaced by their members, in
+    order: a MultiHashVariable under K stands for K/Q and K/R, an
+    AdaptiveEmbeddingVariable for K/hash and K/ev.  Everything else -- an
+    EmbeddingVariable, a DenseTable, and the DenseSlot / ScalarState objects
+    of optimizer.checkpoint_variables -- passes as it is; any other object is
+    a TypeError, a tensor key named twice InvalidArgument."""
+    ev_t, dense_t, scalar_t, mhv_t, adaptive_t = _kinds()
+    out = {}
+
+    def put(key, obj):
+        if key in out:
+            raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
+                                            "tensor key %s is named twice" % key)
+        out[key] = obj
+    for key in variables:
+        v = variables[key]
+        if isinstance(v, mhv_t):
+            put(key + "/Q", v.val_list[0])
+            put(key + "/R", v.val_list[1])
+        elif isinstance(v, adaptive_t):
+            put(key + "/hash", v.hash_table)
+            put(key + "/ev", v.ev)
+        elif isinstance(v, (ev_t, scalar_t)) or isinstance(v, dense_t):
+            put(key, v)
+        else:
+            raise TypeError("checkpoint: %s is %r, not an EmbeddingVariable, a DenseTable, a "
+                            "MultiHashVariable, an AdaptiveEmbeddingVariable or an object of "
+                            "optimizer.checkpoint_variables" % (key, v))
+    return out
+
+
+def _split_kinds(variables):
+    """(expanded dict, its EVs as a dict, its dense objects, its scalars)."""
+    ev_t, dense_t, scalar_t = _kinds()[:3]
+    allv = expand_variables(variables)
+    evs = {k: v for k, v in allv.items() if isinstance(v, ev_t)}
+    dense = {k: v for k, v in allv.items() if isinstance(v, dense_t)}
+    scalars = {k: v for k, v in allv.items() if isinstance(v, scalar_t)}
+    return allv, evs, dense, scalars
+
+
+def _dense_table(obj):
+    """The DenseTable whose update marks a dense object uses."""
+    return getattr(obj, "table", obj)
+
+
+def _scalar_array(s):
+    return np.asarray(s.get(), dtype=np.float32).reshape(())
+
+
+def _check_entry(reader, key, dtype, shape, what):
+    """The bundle holds `key` (NOT_FOUND) with this dtype and shape
+    (InvalidArgument)."""
+    dt, shp = reader.dtype_and_shape(key)
+    if reader.entries[key]["dtype"] == _DT_BFLOAT16 or dt != np.dtype(dtype) \
+            or tuple(shp) != tuple(shape):
+        raise _lib.InvalidArgumentError(
+            _lib.INVALID_ARGUMENT, "%s: %s is %s %s in the checkpoint, the variable is %s %s"
+            % (what, key, dt, list(shp), np.dtype(dtype), list(shape)))
+
+
+def _np_dtype(t):
+    return np.dtype({torch.float32: np.float32, torch.int64: np.int64,
+                     torch.float64: np.float64, torch.int32: np.int32}[t.dtype])
+
+
+def _put_dense(obj, arr):
+    with torch.no_grad():
+        obj.weight.copy_(torch.from_numpy(np.ascontiguousarray(arr)))
+
+
 def save(prefix, variables, global_step=None, compact=False):
-    """Saver.save for EVs: {tensor_key: EmbeddingVariable} -> one bundle.
+    """Saver.save: {tensor_key: variable} -> one bundle.  A variable is an
+    EmbeddingVariable (below), a DenseTable -- one entry `tensor_key`,
+    [rows, dim] in the table's dtype without slices, as a tf.Variable is
+    written -- a MultiHashVariable or AdaptiveEmbeddingVariable (its members,
+    expand_variables), or an object of optimizer.checkpoint_variables: a slot
+    EV, a dense slot (one entry, like its table) or a scalar (one rank-0
+    DT_FLOAT entry).  A dict of EVs alone writes the bytes it always wrote.
 
     Like DumpEv (save_restore_v2_ops.cc:117-133), each variable's key space
     is shrunk first (EmbeddingVar::Shrink: by L2 weight when the EV has an
@@ -501,11 +594,18 @@ def save(prefix, variables, global_step=None, compact=False):
     compact=True also gives the evicted keys' rows back (EmbeddingVariable.
     compact): each distinct key space once, after its shrink and before its
     first dump.  The bundle's bytes do not depend on it."""
+    variables, evs, dense, scalars = _split_kinds(variables)
     w = BundleWriter(prefix)
     compacted = set()
     budgeted = set()
     for name in variables:
         ev = variables[name]
+        if name in dense:
+            w.add(name, ev.weight)
+            continue
+        if name in scalars:
+            w.add(name, _scalar_array(ev))
+            continue
         p = ev._primary or ev
         if p.l2_weight_threshold != -1.0 or (global_step is not None and p.steps_to_live > 0):
             ev.shrink(0 if global_step is None else global_step)
@@ -599,13 +699,31 @@ def restore_embedding_variable(ev, reader, name, partition_id=0, partition_num=1
 
 
 def restore(prefix, variables, partition_id=0, partition_num=1):
-    """Restore {tensor_key: EmbeddingVariable} from a bundle.  A key space with
-    a host-DRAM tier (StorageType.HBM_DRAM) ends within its HBM budget: once
-    all its variables are in, the keys over it are demoted."""
+    """Restore {tensor_key: variable} (the kinds save() takes) from a bundle.
+    A key space with a host-DRAM tier (StorageType.HBM_DRAM) ends within its
+    HBM budget: once all its variables are in, the keys over it are demoted.
+    A dense table, dense slot or scalar whose entry is missing is NOT_FOUND,
+    one whose entry has another shape or dtype InvalidArgument; both (and an
+    unpartitioned EV name without its -keys tensor) are raised before any
+    variable of the call has been changed."""
+    variables, evs, dense, scalars = _split_kinds(variables)
     r = BundleReader(prefix)
+    # every refusal first: nothing is changed by a call that raises one
+    for name, obj in dense.items():
+        _check_entry(r, name, _np_dtype(obj.weight), obj.weight.shape, "restore")
+    for name in scalars:
+        _check_entry(r, name, np.float32, (), "restore")
+    for name in evs:
+        if "part_" not in name:
+            r.dtype_and_shape(name + "-keys")
     for name in variables:
-        restore_embedding_variable(variables[name], r, name, partition_id, partition_num)
-    tiered = {id(ev._primary or ev): (ev._primary or ev) for ev in variables.values()
+        if name in dense:
+            _put_dense(variables[name], r.lookup(name))
+        elif name in scalars:
+            variables[name].set(float(r.lookup(name)))
+        else:
+            restore_embedding_variable(variables[name], r, name, partition_id, partition_num)
+    tiered = {id(ev._primary or ev): (ev._primary or ev) for ev in evs.values()
               if ev.tiered}
     for p in tiered.values():
         p.demote_to()
@@ -648,9 +766,26 @@ def save_incremental(prefix, variables, global_step=None):
     budget are demoted (demote_to, compact=False: they stay in the model and
     out of the removal log) in place of shrink_to, and the delta holds the
     marked keys of both tiers -- the bytes an untiered, unbudgeted trainer
-    that saw the same calls writes.  Returns `prefix`."""
+    that saw the same calls writes.
+
+    Beside EVs the call takes what save() takes.  A dense table or dense slot
+    writes NAME-sparse_incr_keys (int64 [m], the marked row ids ascending) and
+    NAME-sparse_incr_values ([m, dim]; int64 [m] for AdagradDecay's count); a
+    table that is not tracking (DenseTable.track_updates()) is refused by
+    name before anything is shrunk or written, and each table's marks are
+    cleared once, after all of its columns are written.  A scalar is written
+    whole under its own key.  Returns `prefix`."""
+    allv, variables, dense, scalars = _split_kinds(variables)
     for ev in variables.values():
         ev._refuse_tiered("save_incremental")
+    tables = {}
+    for name, obj in dense.items():
+        t = _dense_table(obj)
+        if not t.tracking_updates():
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "save_incremental: dense table %s is not tracking "
+                "updates (track_updates())" % (t.name or name))
+        tables[id(t)] = t
     w = BundleWriter(prefix)
     spaces = {}
     for ev in variables.values():
@@ -671,7 +806,15 @@ def save_incremental(prefix, variables, global_step=None):
                 p.demote_to(p.max_keys, p.policy, compact=False)
             else:
                 p.shrink_to(p.max_keys, p.policy)
-    for name in variables:
+    for name in allv:
+        if name in dense:
+            rows, vals = dense[name].export_updated()
+            w.add(name + "-" + INCR_SUFFIX + "keys", rows)
+            w.add(name + "-" + INCR_SUFFIX + "values", vals)
+            continue
+        if name in scalars:
+            w.add(name, _scalar_array(scalars[name]))
+            continue
         ev = variables[name]
         keys, vals, vers, frqs = ev.export_updated()
         offs, keys, vals, vers, frqs = partition_snapshot(keys, vals, vers, frqs)
@@ -685,6 +828,8 @@ def save_incremental(prefix, variables, global_step=None):
         p.clear_updated()
         if p.tracking_removals():
             p.clear_removed()
+    for t in tables.values():
+        t.clear_updated()
     return prefix
 
 
@@ -707,10 +852,31 @@ def restore_incremental(prefix, variables, partition_id=0, partition_num=1, comp
     is refused, as its track_updates() is, unless it opted in
     (StorageOption(StorageType.HBM_DRAM, incremental=True)): then the removals
     reach both tiers, an upsert promotes its keys first, and the key space
-    ends within its HBM budget (demote_to), as restore() ends."""
+    ends within its HBM budget (demote_to), as restore() ends.  A dense table
+    or dense slot takes its NAME-sparse_incr_{keys, values} through upsert
+    (dr_dense_upsert_rows) and a scalar its whole value; their missing or
+    mis-shaped entries are raised before anything is changed."""
+    allv, variables, dense, scalars = _split_kinds(variables)
     for ev in variables.values():
         ev._refuse_tiered("restore_incremental")
     r = BundleReader(prefix)
+    # the dense objects' and scalars' refusals first, as restore() does
+    for name, obj in dense.items():
+        kname, vname = (name + "-" + INCR_SUFFIX + s for s in ("keys", "values"))
+        m = r.dtype_and_shape(kname)[1]
+        _check_entry(r, kname, np.int64, m, "restore_incremental")
+        _check_entry(r, vname, _np_dtype(obj.weight), tuple(m) + tuple(obj.weight.shape[1:]),
+                     "restore_incremental")
+    for name in scalars:
+        _check_entry(r, name, np.float32, (), "restore_incremental")
+    for name, obj in dense.items():
+        rows = r.lookup(name + "-" + INCR_SUFFIX + "keys")
+        if rows.size:
+            dev = obj.weight.device
+            obj.upsert(torch.as_tensor(rows, device=dev),
+                       torch.as_tensor(r.lookup(name + "-" + INCR_SUFFIX + "values"), device=dev))
+    for name, s in scalars.items():
+        s.set(float(r.lookup(name)))
     sfx = "-" + INCR_SUFFIX + "removed_keys"
     for name in variables:
         ev = variables[name]

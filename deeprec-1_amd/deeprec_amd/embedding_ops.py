@@ -41,14 +41,223 @@ class DenseTable(object):
     ResourceGather path, resource_variable_ops.cc:628).  Sparse gradients are
     queued in pending_grads as IndexedSlices (row ids)."""
 
-    def __init__(self, weight):
+    def __init__(self, weight, name=None):
         self.weight = weight.to(torch.float32).contiguous()
         self.dim = self.weight.shape[1]
         self.device = self.weight.device
         self.pending_grads = []
+        self.name = name
+        self._bits = None       # update marks: int32 [ceil(rows / 32)] on the device
 
     def get_shape(self):
         return tuple(self.weight.shape)
+
+    # -- update tracking (incremental checkpoints; the EV methods' meaning) ----
+    def _refuse_tracking(self):
+        """Why this table's rows cannot be marked and exported on the device,
+        or None."""
+        w = self.weight
+        if w.dtype != torch.float32:
+            return "its rows are %s, the kernels move float32 rows" % (w.dtype,)
+        if not w.is_cuda:
+            return "it lives on %s, the marks and their kernels are on the GPU" % (w.device,)
+        if not _dense_width_ok(w):
+            return ("its row width %d has no kernel shape (up to 1024 when a multiple of 4 and "
+                    "16-byte aligned, else up to 256)" % w.shape[1])
+        return None
+
+    def track_updates(self, on=True):
+        """Start (or stop) recording which rows are updated: one bit per row,
+        set by mark_updated -- the optimizers' apply_gradients marks the
+        gradient's indices, RecordSparseIndices' role -- and read by
+        export_updated.  The table's optimizer slots share the marks.  On while
+        on keeps the marks."""
+        if not on:
+            self._bits = None
+            return
+        why = self._refuse_tracking()
+        if why:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "DenseTable %s cannot track updates: %s"
+                % (self.name or "(unnamed)", why))
+        if self._bits is None:
+            nw = lib().dr_dense_bits_num_words(self.weight.shape[0])
+            self._bits = torch.empty(nw, dtype=torch.int32, device=self.weight.device)
+            self.clear_updated()
+
+    def tracking_updates(self):
+        return self._bits is not None
+
+    def _require_tracking(self, what):
+        if self._bits is None:
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "%s: DenseTable %s is not tracking updates "
+                "(track_updates())" % (what, self.name or "(unnamed)"))
+
+    def mark_updated(self, rows, num_valid=None):
+        """Mark `rows` (the first num_valid of them: device int64[1]) as
+        updated.  Rows outside the table are ignored; a no-op while tracking
+        is off."""
+        mark_dense_grouped([self], [rows], [num_valid])
+
+    def mark_all_updated(self):
+        """Every row marked (a non-lazy optimizer moved them all); a no-op
+        while tracking is off."""
+        if self._bits is not None:
+            with torch.cuda.device(self.weight.device):
+                check(lib().dr_dense_mark_all(ptr(self._bits), self.weight.shape[0],
+                                              stream_handle(self.weight.device)))
+
+    def updated_count(self):
+        """Number of marked rows."""
+        self._require_tracking("updated_count")
+        dev = self.weight.device
+        n = torch.empty(1, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().dr_dense_marked_count(ptr(self._bits), self.weight.shape[0], ptr(n),
+                                              stream_handle(dev)))
+        return int(n.item())
+
+    def export_updated(self):
+        """(rows int64 [m] ascending, values [m, dim]) of the marked rows.
+        Marks are left in place (clear_updated)."""
+        rows, vals = export_marked_columns(self, [self.weight])
+        return rows, vals[0]
+
+    def clear_updated(self):
+        self._require_tracking("clear_updated")
+        with torch.cuda.device(self.weight.device):
+            check(lib().dr_dense_clear_marks(ptr(self._bits), self.weight.shape[0],
+                                             stream_handle(self.weight.device)))
+
+    def upsert(self, rows, values):
+        """weight[rows[i]] = values[i]: how a delta is applied.  Rows must be
+        distinct; a row outside the table is skipped and latches
+        InvalidArgument for status_check."""
+        upsert_dense_rows(self.weight, rows, values)
+
+
+def _dense_width_ok(w):
+    """dr_dense_apply_grouped's row shapes (dense_apply.hip da_shape)."""
+    d = w.shape[1]
+    return 1 <= d <= 256 or (d % 4 == 0 and d <= 1024 and w.data_ptr() % 16 == 0)
+
+
+def mark_dense_grouped(tables, rows, num_valid=None):
+    """dr_dense_mark_rows over (table, row ids[, device count]) triples: one
+    call per device for every tracking table among them, nothing read back."""
+    import ctypes as C
+    nv = num_valid if num_valid is not None else [None] * len(tables)
+    groups = {}
+    for t, r, n in zip(tables, rows, nv):
+        if t._bits is None:
+            continue
+        r = r.reshape(-1).to(device=t.weight.device, dtype=torch.int64).contiguous()
+        groups.setdefault(str(t.weight.device), []).append((t, r, n))
+    for grp in groups.values():
+        dev = grp[0][0].weight.device
+        descs = (_lib.DrDenseMarkDesc * len(grp))()
+        for d, (t, r, n) in zip(descs, grp):
+            d.bits, d.rows = t._bits.data_ptr(), t.weight.shape[0]
+            d.idx, d.n, d.n_dev = r.data_ptr(), r.numel(), ptr(n)
+        with torch.cuda.device(dev):
+            check(lib().dr_dense_mark_rows(descs, len(grp), stream_handle(dev)))
+
+
+def export_marked_columns(table, columns):
+    """dr_dense_export_marked of a tracking table: (rows int64 [m] ascending,
+    [values [m, dim] per column]) for up to DENSE_MAX_COLS [rows, dim] fp32
+    blocks that share the table's marks (the table and its slots)."""
+    import ctypes as C
+    table._require_tracking("export_updated")
+    dev = table.weight.device
+    nrows, dim = table.weight.shape
+    for c in columns:
+        if tuple(c.shape) != (nrows, dim) or c.dtype != torch.float32 or c.device != dev \
+                or not c.is_contiguous():
+            raise _lib.InvalidArgumentError(
+                _lib.INVALID_ARGUMENT, "export_updated: a column of DenseTable %s is not a "
+                "contiguous float32 %s block on %s" % (table.name or "(unnamed)",
+                                                       (nrows, dim), dev))
+    m = table.updated_count()
+    rows = torch.empty(m, dtype=torch.int64, device=dev)
+    vals = [torch.empty((m, dim), dtype=torch.float32, device=dev) for _ in columns]
+    if m == 0:
+        return rows, vals
+    m_dev = torch.empty(1, dtype=torch.int64, device=dev)
+    P = C.c_void_p * len(columns)
+    with torch.cuda.device(dev):
+        wsb = lib().dr_dense_export_marked_workspace_size(nrows)
+        ws = workspace(wsb, dev)
+        check(lib().dr_dense_export_marked(
+            ptr(table._bits), nrows, dim, P(*[c.data_ptr() for c in columns]), len(columns), m,
+            ptr(rows), P(*[v.data_ptr() for v in vals]), ptr(m_dev), ptr(ws), wsb,
+            stream_handle(dev)))
+    return rows, vals
+
+
+def upsert_dense_rows(column, rows, values):
+    """dr_dense_upsert_rows on one [rows, dim] fp32 device block (a CPU block,
+    or one the kernels have no shape for, takes torch indexing)."""
+    import ctypes as C
+    r = rows.reshape(-1).to(device=column.device, dtype=torch.int64).contiguous()
+    v = values.reshape(r.numel(), column.shape[1]).to(device=column.device,
+                                                      dtype=column.dtype).contiguous()
+    if r.numel() == 0:
+        return
+    if not (column.is_cuda and column.dtype == torch.float32 and _dense_width_ok(column)
+            and (column.shape[1] <= 256 or v.data_ptr() % 16 == 0)):
+        with torch.no_grad():
+            column[r] = v
+        return
+    P = C.c_void_p * 1
+    with torch.cuda.device(column.device):
+        check(lib().dr_dense_upsert_rows(P(column.data_ptr()), 1, column.shape[0],
+                                         column.shape[1], ptr(r), r.numel(), None,
+                                         P(v.data_ptr()), stream_handle(column.device)))
+
+
+class DenseSlot(object):
+    """An optimizer slot of a DenseTable as a checkpoint object: a tensor with
+    one entry per table row ([rows, dim] fp32, or AdagradDecay's int64 [rows]
+    count) that shares its table's update marks, as an EV slot shares its key
+    space."""
+
+    def __init__(self, table, weight, name=None):
+        self.table = table
+        self.weight = weight
+        self.name = name
+        self.device = weight.device
+
+    def tracking_updates(self):
+        return self.table.tracking_updates()
+
+    def export_updated(self):
+        w = self.weight
+        if w.dim() == 2 and w.dtype == torch.float32 and w.shape == self.table.weight.shape:
+            rows, vals = export_marked_columns(self.table, [w])
+            return rows, vals[0]
+        rows, _ = export_marked_columns(self.table, [])
+        return rows, w[rows]
+
+    def upsert(self, rows, values):
+        w = self.weight
+        if w.dim() == 2:
+            upsert_dense_rows(w, rows, values)
+        else:
+            r = rows.reshape(-1).to(device=w.device, dtype=torch.int64)
+            w[r] = values.reshape(-1).to(device=w.device, dtype=w.dtype)
+
+
+class ScalarState(object):
+    """A non-slot optimizer scalar (a beta power) as a checkpoint object:
+    get() -> the value as a host float, set(v) installs it everywhere the
+    optimizer keeps it."""
+
+    def __init__(self, get, set, name=None):
+        self.get = get
+        self.set = set
+        self.name = name
 
 
 def _anchor(holder):

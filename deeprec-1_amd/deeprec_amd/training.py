@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 from ._lib import check, lib, ptr, stream_handle
-from .embedding_ops import DenseTable
+from .embedding_ops import DenseSlot, DenseTable, ScalarState, mark_dense_grouped
 from .kv_variable_ops import (AdaptiveEmbeddingVariable, EmbeddingVariable, IndexedSlices,
                               MultiHashVariable, PendingRowSlices, _flush_deferred_releases,
                               _mark_updated_hbm, mark_updated_rows_grouped)
@@ -174,7 +174,7 @@ class _Optimizer(object):
     def apply_gradients(self, var_list, global_step=None):
         gs = -1 if global_step is None else int(global_step)
         var_list = _expand_multihash(var_list)
-        late = self._record_updates(var_list)
+        late = self._record_updates(var_list, self._dense_marks_all)
         if self._opt == 0 and _KNOWN_ROWS:
             self._apply_fused_rows(var_list, gs)
         rounds = []   # rounds[r] = [(var, slices)] applied in one grouped launch
@@ -207,8 +207,35 @@ class _Optimizer(object):
         self._finish()
         _flush_deferred_releases()   # EVs collected meanwhile (no-op while capturing)
 
+    # dense tables with pending gradients are marked whole (a non-lazy optimizer)
+    _dense_marks_all = False
+
     @staticmethod
-    def _record_updates(var_list):
+    def _record_dense_updates(var_list, dense_all=False):
+        """The dense case of _record_updates: every tracking DenseTable with
+        pending gradients is marked from its pending slices' indices,
+        honouring num_valid, before they are consumed -- one
+        dr_dense_mark_rows per device for all of them, no host read.
+        dense_all (AdamOptimizer: dense Adam is non-lazy, every row moves)
+        marks such a table whole.  Nothing runs for a table that is not
+        tracking."""
+        marks = [(var, sl) for var in var_list
+                 if isinstance(var, DenseTable) and var.tracking_updates()
+                 for sl in var.pending_grads]
+        if not marks:
+            return
+        if dense_all:
+            seen = set()
+            for var, _ in marks:
+                if id(var) not in seen:
+                    seen.add(id(var))
+                    var.mark_all_updated()
+            return
+        mark_dense_grouped([var for var, _ in marks], [sl.indices for _, sl in marks],
+                           [sl.num_valid for _, sl in marks])
+
+    @staticmethod
+    def _record_updates(var_list, dense_all=False):
         """RecordSparseIndices' role (incremental_saver.py): every EV whose key
         space tracks updates gets the indices of its pending slices marked
         (honouring num_valid) before they are consumed.  Reading the indices
@@ -225,7 +252,11 @@ class _Optimizer(object):
         mark_updated_grouped's arguments, or None: the mark skips a key whose
         primary row is untouched, and in a Counter-filter EV the apply itself
         admits a key whose freq has reached filter_freq -- marked before it,
-        the key's first update would be missing from the next delta."""
+        the key's first update would be missing from the next delta.
+
+        Dense tables that track updates are marked first
+        (_record_dense_updates; dense_all: whole)."""
+        _Optimizer._record_dense_updates(var_list, dense_all)
         marks = [(var, sl) for var in var_list
                  if isinstance(var, EmbeddingVariable) and var.tracking_updates()
                  for sl in var.pending_grads]
@@ -290,6 +321,47 @@ class _Optimizer(object):
 
     def _slots(self, var):
         return None, None
+
+    # -- checkpoints: the optimizer's state of a set of variables -------------
+    _slot_names = ()    # the slot columns' names (var.slot's), in _slots order
+
+    def _dense_state(self, var):
+        """The slot tensors of a dense table in _slot_names order, created
+        with the values the first apply would give them."""
+        return ()
+
+    def _var_scalars(self, key, var):
+        """{tensor_key: ScalarState} of the per-variable non-slot state."""
+        return {}
+
+    def _global_scalars(self):
+        """{tensor_key: ScalarState} of the optimizer's own non-slot state."""
+        return {}
+
+    def checkpoint_variables(self, variables):
+        """The optimizer's state of `variables` (the dict checkpoint.save
+        takes; a MultiHashVariable under K stands for K/Q and K/R, an
+        AdaptiveEmbeddingVariable for K/hash and K/ev) as {tensor_key: object}
+        for checkpoint.save / restore / save_incremental / restore_incremental:
+        KEY/<slot> -> the slot EV of an EmbeddingVariable, or a DenseSlot that
+        shares its DenseTable's update marks, and the beta powers as
+        ScalarStates.  State that does not exist yet is created with the value
+        the first apply would give it, so a fresh optimizer can be restored
+        into."""
+        from .checkpoint import expand_variables
+        out = {}
+        for key, var in expand_variables(variables).items():
+            if isinstance(var, EmbeddingVariable):
+                for name, slot in zip(self._slot_names, self._slots(var)):
+                    out["%s/%s" % (key, name)] = slot
+            elif isinstance(var, DenseTable):
+                for name, t in zip(self._slot_names, self._dense_state(var)):
+                    out["%s/%s" % (key, name)] = DenseSlot(var, t, "%s/%s" % (key, name))
+            else:
+                raise TypeError("checkpoint_variables: unsupported variable %r" % (var,))
+            out.update(self._var_scalars(key, var))
+        out.update(self._global_scalars())
+        return out
 
     def _scalars(self):
         return (0.0, 0.0, 0.0, 0.0, 0.0)
@@ -427,6 +499,11 @@ class AdagradOptimizer(_Optimizer):
     def _slots(self, var):
         return var.slot("Adagrad", self.init_acc), None
 
+    _slot_names = ("Adagrad",)
+
+    def _dense_state(self, var):
+        return (self._dense_slots(var)[0],)
+
     def _dense_update(self, var, idx, g):
         acc = self._dense_acc.setdefault(id(var), torch.full_like(var.weight, self.init_acc))
         a = acc[idx] + g * g
@@ -461,6 +538,28 @@ class AdamOptimizer(_Optimizer):
 
     def _slots(self, var):
         return var.slot("Adam", 0.0), var.slot("Adam_1", 0.0)
+
+    _slot_names = ("Adam", "Adam_1")
+    _dense_marks_all = True   # _dense_update moves every row of the table
+
+    def _dense_state(self, var):
+        w = var.weight
+        return self._dense_mv.setdefault(id(var), (torch.zeros_like(w), torch.zeros_like(w)))
+
+    def _global_scalars(self):
+        """beta1_power / beta2_power: one pair.  Read from the device copies
+        where there are any (the source of truth once steps replay from a
+        graph); restoring sets the host values and every device copy."""
+        self.sync_host_powers()
+
+        def setter(attr, i):
+            def put(v):
+                setattr(self, attr, float(v))
+                for pw, _ in self._pw.values():
+                    pw[i].fill_(float(v))
+            return put
+        return {"beta1_power": ScalarState(lambda: self.b1p, setter("b1p", 0), "beta1_power"),
+                "beta2_power": ScalarState(lambda: self.b2p, setter("b2p", 1), "beta2_power")}
 
     def _scalars(self):
         return (self.b1p, self.b2p, self.beta1, self.beta2, self.eps)
@@ -579,6 +678,13 @@ class FtrlOptimizer(_Optimizer):
     def _slots(self, var):
         return var.slot("Ftrl", self.init_acc), var.slot("Ftrl_1", 0.0)
 
+    _slot_names = ("Ftrl", "Ftrl_1")
+
+    def _dense_state(self, var):
+        w = var.weight
+        return self._dense.setdefault(
+            id(var), (torch.full_like(w, self.init_acc), torch.zeros_like(w)))
+
     def _apply_ev_batch(self, items, gs):
         import ctypes as C
         groups = {}
@@ -672,6 +778,20 @@ class AdamAsyncOptimizer(_Optimizer):
 
     def _slots(self, var):
         return var.slot("AdamAsync", 0.0), var.slot("AdamAsync_1", 0.0)
+
+    _slot_names = ("AdamAsync", "AdamAsync_1")
+
+    def _dense_state(self, var):
+        return self._dense_slots(var)[:2]
+
+    def _var_scalars(self, key, var):
+        """KEY/beta1_power, KEY/beta2_power: the variable's own pair."""
+        p = self._power_t(var)
+
+        def state(i, name):
+            return ScalarState(lambda: p[i].item(), lambda v: p[i].fill_(float(v)), name)
+        return {key + "/beta1_power": state(0, key + "/beta1_power"),
+                key + "/beta2_power": state(1, key + "/beta2_power")}
 
     def _power_t(self, var):
         dev = var.weight.device if isinstance(var, DenseTable) else var.device
@@ -781,6 +901,15 @@ class AdagradDecayOptimizer(_Optimizer):
 
     def _slots(self, var):
         return var.slot("AdagradDecay", self.init_acc), var.slot("AdagradDecay_1", 0.0)
+
+    _slot_names = ("AdagradDecay", "AdagradDecay_1")
+
+    def _dense_state(self, var):
+        """(accumulator [rows, dim], decay count int64 [rows])."""
+        w = var.weight
+        return self._dense.setdefault(
+            id(var), (torch.full_like(w, self.init_acc),
+                      torch.zeros(w.shape[0], dtype=torch.int64, device=w.device)))
 
     def _apply_ev_batch(self, items, gs):
         import ctypes as C

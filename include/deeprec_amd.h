@@ -1950,6 +1950,66 @@ int dr_adaptive_grad(const float* gu, int dim, const int32_t* mask_u, const int6
                      const int64_t* num_ev, float* ev_val, int64_t* hash_idx, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Update marks and row export of dense tables (checkpoints and deltas of a  */
+/* DenseTable and of its optimizer slots; the dense counterpart of           */
+/* dr_ev_mark_updated_rows / dr_ev_export_updated).  The marks of a table    */
+/* are one bit per row in dr_dense_bits_num_words(rows) uint32 words of      */
+/* CALLER-OWNED device memory (csrc/dr_dense_bits.h: bit row & 31 of word    */
+/* row >> 5).  The bits of the last word at or past `rows` are never set by  */
+/* these entries and are ignored where something else set them.  None of the */
+/* entries allocates, synchronises or reads anything back, so each may sit   */
+/* in a captured step.  Null or inconsistent arguments, rows < 1, a row      */
+/* width outside the shapes of dr_dense_apply_grouped (up to 1024 floats     */
+/* when a multiple of 4 and every column pointer 16-byte aligned, else up to */
+/* 256), more than DR_DENSE_MAX_COLS columns, a negative capacity or count   */
+/* and a short workspace are DR_INVALID_ARGUMENT before any device is        */
+/* touched.                                                                  */
+/* ------------------------------------------------------------------------ */
+#define DR_DENSE_MAX_COLS 4
+/* Number of uint32 words of the marks of `rows` rows (0 for rows <= 0).    */
+int64_t dr_dense_bits_num_words(int64_t rows);
+/* Mark.  With N = min(n, *n_dev) (n alone when n_dev is NULL), every idx[i], */
+/* i < N, with 0 <= idx[i] < rows gets its bit set.  A negative index, an    */
+/* index >= rows and everything at or past N is skipped: nothing there is    */
+/* read as a row id and no address is formed from it.  No error is latched   */
+/* for an index out of range (the apply that follows does that).  A          */
+/* descriptor with bits == NULL is skipped.  Any number of descriptors,      */
+/* DR_MAX_GROUP per launch; several may name the same marks.  n and the n of */
+/* one launch must stay below 2^31.                                          */
+typedef struct {
+  uint32_t* bits;          /* the table's marks, or NULL: skip               */
+  int64_t rows;
+  const int64_t* idx;      /* [n] row ids                                    */
+  int64_t n;               /* capacity                                       */
+  const int64_t* n_dev;    /* optional DEVICE count                          */
+} dr_dense_mark_desc;
+int dr_dense_mark_rows(const dr_dense_mark_desc* descs_host, int num_tables, void* stream);
+/* Mark every row in [0, rows) (the tail bits of the last word are written   */
+/* as 0), and clear every mark.  Both are kernels, not memset nodes.         */
+int dr_dense_mark_all(uint32_t* bits, int64_t rows, void* stream);
+int dr_dense_clear_marks(uint32_t* bits, int64_t rows, void* stream);
+/* *count_dev (DEVICE int64) = the number of marked rows in [0, rows).       */
+int dr_dense_marked_count(const uint32_t* bits, int64_t rows, int64_t* count_dev, void* stream);
+/* Export.  With m marked rows r_0 < r_1 < ... in [0, rows): *m_dev = m (the */
+/* full count, so the caller sees an overflow), and for j < min(m, capacity) */
+/* rows_out[j] = r_j and vals_out[c][j, :] = cols[c][r_j, :] for each of the */
+/* num_cols (0 .. DR_DENSE_MAX_COLS) columns: `cols` and `vals_out` are HOST */
+/* arrays of device pointers to [rows, dim] and [capacity, dim] fp32 blocks. */
+/* Nothing is written at or past `capacity`.  rows must be below 2^31.       */
+size_t dr_dense_export_marked_workspace_size(int64_t rows);
+int dr_dense_export_marked(const uint32_t* bits, int64_t rows, int dim, const float* const* cols,
+                           int num_cols, int64_t capacity, int64_t* rows_out,
+                           float* const* vals_out, int64_t* m_dev, void* ws, size_t ws_bytes,
+                           void* stream);
+/* Upsert.  cols[c][idx[i], :] = vals[c][i, :] for i < N = min(n, *n_dev)    */
+/* and every column c < num_cols (1 .. DR_DENSE_MAX_COLS).  An index outside */
+/* [0, rows) is skipped and latches DR_INVALID_ARGUMENT (dr_status_check),   */
+/* as dr_gather does.  The indices must be distinct.                         */
+int dr_dense_upsert_rows(float* const* cols, int num_cols, int64_t rows, int dim,
+                         const int64_t* idx, int64_t n, const int64_t* n_dev,
+                         const float* const* vals, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Checkpoint support (host function, no device work): crc32c::Extend of    */
 /* core/lib/hash/crc32c.h, used for TensorBundle entry and SSTable block     */
 /* checksums (core/util/tensor_bundle/tensor_bundle.cc:435-455).             */
