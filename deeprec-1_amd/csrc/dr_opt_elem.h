@@ -112,4 +112,53 @@ __device__ __forceinline__ float adagrad_decay_one(float gv, float w, float* a1,
   return w - up;
 }
 
+// Dense FTRL element (ResourceSparseApplyFtrl[V2], training_ops.cc:2587-2614):
+// elementwise, the clip is on the element's own linear (the KV op's row norm
+// is ev_apply_ftrl_kernel's).  g is the row's summed gradient; accum takes the
+// plain g, linear the shrunk one (V2).  P(x) = sqrt(x) when lr_power == -0.5,
+// else x^(-lr_power) (ftrl_pow's selection).
+__device__ __forceinline__ float ftrl_dense_one(float gv, float w, float* a1, float* a2,
+                                                const OptScalars& sc) {
+  const float a = *a1;
+  float lin = *a2;
+  float gu = gv;
+  if (sc.l2_shrinkage > 0.0f) {
+    const float sh = (2.0f * sc.l2_shrinkage) * w;
+    gu = gv + sh;
+  }
+  const float g2 = gv * gv;
+  const float na = a + g2;
+  const bool root = sc.lr_power == -0.5f;
+  const float pn = root ? sqrtf(na) : powf(na, -sc.lr_power);
+  const float po = root ? sqrtf(a) : powf(a, -sc.lr_power);
+  const float dp = pn - po;
+  const float q = dp / sc.lr;
+  const float t = q * w;
+  const float d = gu - t;
+  lin = lin + d;
+  const float y0 = pn / sc.lr;
+  const float y = y0 + 2.0f * sc.l2;
+  float c = lin < -sc.l1 ? -sc.l1 : lin;   // min(max(lin, -l1), l1); a NaN stays
+  c = c > sc.l1 ? sc.l1 : c;
+  const float num = c - lin;
+  *a1 = na;
+  *a2 = lin;
+  return num / y;
+}
+
+// Dense Adam (adam.py _apply_sparse_shared, TF's non-lazy sparse Adam) on a
+// row no gradient names: m and v decay and the row still moves.  Nothing is
+// added to m (m * beta1 + 0.0f would turn a -0.0 into +0.0).  A named row
+// takes apply_one<OPT_ADAM_ASYNC>, the same arithmetic with the gradient in.
+__device__ __forceinline__ float adam_unnamed_one(float w, float* a1, float* a2,
+                                                  const OptScalars& sc) {
+  const float m = *a1 * sc.beta1;
+  const float v = *a2 * sc.beta2;
+  const float num = m * sc.alpha;
+  const float den = sqrtf(v) + sc.eps;
+  *a1 = m;
+  *a2 = v;
+  return w - num / den;
+}
+
 }  // namespace dr

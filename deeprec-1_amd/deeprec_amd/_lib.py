@@ -102,6 +102,16 @@ class DrDenseApplyDesc(C.Structure):
     ]
 
 
+class DrDenseApplyOpts(C.Structure):
+    """dr_dense_apply_opts (include/deeprec_amd.h): the scalars of dense FTRL
+    and AdagradDecay for dr_dense_apply_grouped_ex."""
+    _fields_ = [
+        ("l1", C.c_float), ("l2", C.c_float), ("lr_power", C.c_float),
+        ("l2_shrinkage", C.c_float), ("decay_rate", C.c_float), ("decay_baseline", C.c_float),
+        ("decay_step", C.c_int64), ("global_step", C.c_int64),
+    ]
+
+
 DENSE_MAX_COLS = 4
 
 
@@ -446,6 +456,9 @@ SIGNATURES = {
                            _P]),
     "dr_dense_apply_grouped_workspace_size": (_SZ, [_P, _I32]),
     "dr_dense_apply_grouped": (_I32, [_I32, _P, _I32, _F32, _F32, _F32, _F32, _P, _SZ, _P]),
+    "dr_dense_apply_grouped_ex_workspace_size": (_SZ, [_I32, _P, _I32]),
+    "dr_dense_apply_grouped_ex": (_I32, [_I32, _P, _I32, _F32, _F32, _F32, _F32, _P, _P, _SZ,
+                                         _P]),
     "dr_dense_bits_num_words": (_I64, [_I64]),
     "dr_dense_mark_rows": (_I32, [_P, _I32, _P]),
     "dr_dense_mark_all": (_I32, [_P, _I64, _P]),

@@ -83,9 +83,10 @@ def _rounds(slices):
 # SGD applies of row-grouped backwards use the forward's rows (A/B switch)
 _KNOWN_ROWS = os.environ.get("DR_APPLY_PROBE") != "1"
 
-# Dense tables of SGD / Adagrad / AdamAsync are applied by the grouped HIP
-# apply (dr_dense_apply_grouped: dedup and update on the device, the count
-# read there, capturable).  A/B switch DR_DENSE_APPLY=torch: unique +
+# Dense tables are applied by the grouped HIP apply (dr_dense_apply_grouped for
+# SGD / Adagrad / AdamAsync, dr_dense_apply_grouped_ex for Adam / FTRL /
+# AdagradDecay: dedup and update on the device, the count read there,
+# capturable).  A/B switch DR_DENSE_APPLY=torch: unique +
 # unsorted_segment_sum + torch indexing (_apply_dense), one host read per table
 _NATIVE_DENSE = os.environ.get("DR_DENSE_APPLY", "native") != "torch"
 
@@ -158,7 +159,7 @@ def _dense_slice(pending, count_gate):
 
 class _Optimizer(object):
     _opt = None   # DR_OPT_* code of the EV apply kernel
-    _dense_opt = None   # DR_OPT_* code of dr_dense_apply_grouped (None: torch path only)
+    _dense_opt = None   # DR_OPT_* code of dr_dense_apply_grouped[_ex] (None: torch path only)
 
     def __init__(self, learning_rate, use_locking=False):
         self.lr = float(learning_rate)
@@ -422,8 +423,8 @@ class _Optimizer(object):
         self._dense_update(var, idx, val)
 
     def _dense_native(self, var):
-        """The table takes dr_dense_apply_grouped: one of its optimizers, fp32
-        rows on a GPU, a row width it has a shape for."""
+        """The table takes dr_dense_apply_grouped[_ex]: fp32 rows on a GPU, a
+        row width it has a shape for."""
         w = var.weight
         return (_NATIVE_DENSE and self._dense_opt is not None and w.is_cuda
                 and w.dtype == torch.float32 and w.is_contiguous()
@@ -438,9 +439,15 @@ class _Optimizer(object):
     def _dense_scalars(self):
         return 0.0, 0.0, 0.0   # beta1, beta2, epsilon
 
+    def _dense_opts(self):
+        """The dr_dense_apply_opts of an optimizer that goes through
+        dr_dense_apply_grouped_ex (Adam, FTRL, AdagradDecay), else None."""
+        return None
+
     def _apply_dense_grouped(self, items):
-        """One dr_dense_apply_grouped per device over every dense table with
-        pending gradients: nothing is read back, so the step can be captured."""
+        """One dr_dense_apply_grouped[_ex] per device over every dense table
+        with pending gradients: nothing is read back, so the step can be
+        captured."""
         import ctypes as C
         from ._lib import DrDenseApplyDesc, workspace
         groups = {}
@@ -460,11 +467,21 @@ class _Optimizer(object):
                 d.table, d.rows, d.dim = var.weight.data_ptr(), var.weight.shape[0], var.dim
                 d.slot1, d.slot2, d.powers = ptr(s1), ptr(s2), ptr(pw)
                 d.grad, d.idx, d.n, d.n_dev = v.data_ptr(), i.data_ptr(), i.numel(), ptr(n_dev)
+            opts = self._dense_opts()
             with torch.cuda.device(dev):
-                wsb = lib().dr_dense_apply_grouped_workspace_size(descs, len(grp))
-                ws = workspace(wsb, dev)
-                check(lib().dr_dense_apply_grouped(self._dense_opt, descs, len(grp), self.lr, b1,
-                                                   b2, eps, ptr(ws), wsb, stream_handle(dev)))
+                if opts is None:
+                    wsb = lib().dr_dense_apply_grouped_workspace_size(descs, len(grp))
+                    ws = workspace(wsb, dev)
+                    check(lib().dr_dense_apply_grouped(self._dense_opt, descs, len(grp), self.lr,
+                                                       b1, b2, eps, ptr(ws), wsb,
+                                                       stream_handle(dev)))
+                else:
+                    wsb = lib().dr_dense_apply_grouped_ex_workspace_size(self._dense_opt, descs,
+                                                                         len(grp))
+                    ws = workspace(wsb, dev)
+                    check(lib().dr_dense_apply_grouped_ex(self._dense_opt, descs, len(grp),
+                                                          self.lr, b1, b2, eps, C.byref(opts),
+                                                          ptr(ws), wsb, stream_handle(dev)))
             ops._post(dev)
 
 
@@ -526,6 +543,7 @@ class AdamOptimizer(_Optimizer):
     once per apply_gradients like the optimizer's non-slot variables."""
 
     _opt = 2
+    _dense_opt = 2   # DR_OPT_ADAM of dr_dense_apply_grouped_ex
 
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8,
                  use_locking=False):
@@ -545,6 +563,20 @@ class AdamOptimizer(_Optimizer):
     def _dense_state(self, var):
         w = var.weight
         return self._dense_mv.setdefault(id(var), (torch.zeros_like(w), torch.zeros_like(w)))
+
+    def _dense_slots(self, var):
+        """m, v and the optimizer's device beta powers: the native apply forms
+        lr_t from them on the device (capturable once they exist: one eager
+        step or prepare(device)); _finish advances them."""
+        m, v = self._dense_state(var)
+        return m, v, self._device_powers(var.weight.device)
+
+    def _dense_scalars(self):
+        return self.beta1, self.beta2, self.eps
+
+    def _dense_opts(self):
+        from ._lib import DrDenseApplyOpts
+        return DrDenseApplyOpts()
 
     def _global_scalars(self):
         """beta1_power / beta2_power: one pair.  Read from the device copies
@@ -585,8 +617,9 @@ class AdamOptimizer(_Optimizer):
         in _finish by an fp32 multiply on the device: the same roundings as the
         host values, and no per-step host scalar in the EV apply (capturable).
         Under replays only these advance; sync_host_powers() brings the host
-        copies (used by dense tables and the DR_KV_ADAM_DEVICE_POWERS=0 A/B
-        path, neither graph-safe) up to date."""
+        copies (used by the torch arm of dense tables and the
+        DR_KV_ADAM_DEVICE_POWERS=0 A/B path, neither graph-safe) up to date.
+        Dense tables on the native apply read these device powers too."""
         key = str(dev)
         if key not in self._pw:
             if _capturing():
@@ -640,7 +673,9 @@ class AdamOptimizer(_Optimizer):
         """_apply_sparse_shared (adam.py:183-207) on a dense table: m and v
         decay on every row, the deduplicated gradient is scatter-added, and
         every row of var moves by lr_t * m / (sqrt(v) + eps) (TF's non-lazy
-        sparse Adam), lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)."""
+        sparse Adam), lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t).  The torch
+        arm (DR_DENSE_APPLY=torch, CPU tensors, unsupported widths) of the
+        native apply (dr_dense_apply_grouped_ex, DR_OPT_ADAM)."""
         _not_capturing("AdamOptimizer on a dense table (lr_t from host beta powers)")
         w = var.weight
         m, v = self._dense_mv.setdefault(id(var), (torch.zeros_like(w), torch.zeros_like(w)))
@@ -663,6 +698,7 @@ class FtrlOptimizer(_Optimizer):
     of training_ops.cc (per-element |linear| instead of the KV op's row norm)."""
 
     _opt = 3
+    _dense_opt = 5   # DR_OPT_FTRL of dr_dense_apply_grouped_ex
 
     def __init__(self, learning_rate, learning_rate_power=-0.5, initial_accumulator_value=0.1,
                  l1_regularization_strength=0.0, l2_regularization_strength=0.0,
@@ -684,6 +720,15 @@ class FtrlOptimizer(_Optimizer):
         w = var.weight
         return self._dense.setdefault(
             id(var), (torch.full_like(w, self.init_acc), torch.zeros_like(w)))
+
+    def _dense_slots(self, var):
+        acc, lin = self._dense_state(var)
+        return acc, lin, None
+
+    def _dense_opts(self):
+        from ._lib import DrDenseApplyOpts
+        return DrDenseApplyOpts(l1=self.l1, l2=self.l2, lr_power=self.lr_power,
+                                l2_shrinkage=self.l2_shrinkage)
 
     def _apply_ev_batch(self, items, gs):
         import ctypes as C
@@ -874,6 +919,8 @@ class AdagradDecayOptimizer(_Optimizer):
     optimizer's _global_step_on_worker, :140), which also stamps versions.
     Dense tables: SparseApplyAdagradDecay (:495-670) with one count per row."""
 
+    _dense_opt = 6   # DR_OPT_ADAGRAD_DECAY of dr_dense_apply_grouped_ex
+
     def __init__(self, learning_rate, global_step=None, initial_accumulator_value=0.1,
                  accumulator_decay_step=100000, accumulator_decay_rate=0.9, use_locking=False):
         if initial_accumulator_value <= 0.0:
@@ -910,6 +957,16 @@ class AdagradDecayOptimizer(_Optimizer):
         return self._dense.setdefault(
             id(var), (torch.full_like(w, self.init_acc),
                       torch.zeros(w.shape[0], dtype=torch.int64, device=w.device)))
+
+    def _dense_slots(self, var):
+        acc, count = self._dense_state(var)
+        return acc, count, None
+
+    def _dense_opts(self):
+        # the step goes in by value, as into the EV apply (frozen in a capture)
+        from ._lib import DrDenseApplyOpts
+        return DrDenseApplyOpts(decay_rate=self.decay_rate, decay_baseline=self.init_acc,
+                                decay_step=self.decay_step, global_step=self._gs)
 
     def _apply_ev_batch(self, items, gs):
         import ctypes as C

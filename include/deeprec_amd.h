@@ -974,7 +974,11 @@ enum {
   DR_OPT_ADAGRAD = 1,
   DR_OPT_ADAM = 2,
   DR_OPT_ADAM_ASYNC = 3,
-  DR_OPT_ADAM_ASYNC_RMSPROP = 4
+  DR_OPT_ADAM_ASYNC_RMSPROP = 4,
+  /* dr_dense_apply_grouped_ex only (dr_ev_apply_grouped refuses them: the EV */
+  /* FTRL / AdagradDecay applies have entries of their own)                   */
+  DR_OPT_FTRL = 5,
+  DR_OPT_ADAGRAD_DECAY = 6
 };
 int dr_ev_apply_grouped(int optimizer, dr_ev* const* vars, dr_ev* const* slot1,
                         dr_ev* const* slot2, int num_tables, const float* const* grads,
@@ -1886,7 +1890,7 @@ typedef struct {
   int32_t dim;
   float* slot1;            /* [rows, dim] fp32 or NULL (see optimizer)       */
   float* slot2;
-  float* powers;           /* device float[2], DR_OPT_ADAM_ASYNC only        */
+  float* powers;           /* device float[2], DR_OPT_ADAM_ASYNC / DR_OPT_ADAM */
   const float* grad;       /* [n, dim]                                       */
   const int64_t* idx;      /* [n] row ids; may repeat; < 0 = skip            */
   int64_t n;               /* capacity                                       */
@@ -1897,6 +1901,60 @@ size_t dr_dense_apply_grouped_workspace_size(const dr_dense_apply_desc* descs_ho
 int dr_dense_apply_grouped(int optimizer, const dr_dense_apply_desc* descs_host, int num_tables,
                            float lr, float beta1, float beta2, float epsilon, void* ws,
                            size_t ws_bytes, void* stream);
+
+/* The same call for every optimizer of a dense table: the four codes above, */
+/* with exactly the results of dr_dense_apply_grouped (opts may be NULL), and */
+/* DR_OPT_ADAM, DR_OPT_FTRL, DR_OPT_ADAGRAD_DECAY.  Everything said above     */
+/* holds (N, the serial sum per distinct row, skipped and latched indices,    */
+/* launch groups, no allocation / synchronisation / read-back: capturable).   */
+/* The element updates are the reference's scalar formulas with separate fp32 */
+/* roundings, g the row's summed gradient.                                    */
+/*  DR_OPT_FTRL -- ResourceSparseApplyFtrl[V2], elementwise (the clip is on    */
+/*    the element's own linear; the KV op's row norm is                       */
+/*    dr_ev_apply_ftrl_grouped's).  slot1 = accum, slot2 = linear, opts       */
+/*    required, lr != 0.  Per element of a named row:                         */
+/*      gu  = l2_shrinkage > 0 ? g + (2 l2_shrinkage) w : g                   */
+/*      na  = accum + g g                    (plain g)                        */
+/*      pn  = P(na), po = P(accum);  P(x) = sqrt(x) when lr_power == -0.5,    */
+/*                                          else powf(x, -lr_power)           */
+/*      linear += gu - ((pn - po) / lr) w                                     */
+/*      w = (min(max(linear, -l1), l1) - linear) / (pn / lr + 2 l2)           */
+/*      accum = na                                                            */
+/*  DR_OPT_ADAGRAD_DECAY -- SparseApplyAdagradDecay with one decay count per   */
+/*    row.  slot1 = accumulator; slot2 is the table's int64 [rows] count,     */
+/*    passed through a cast (8-byte aligned); opts required, decay_step > 0,  */
+/*    global_step as dr_ev_apply_adagrad_decay_grouped takes it.  A named row */
+/*    decays (accum = max(accum * decay_rate, decay_baseline) before accum += */
+/*    g g) iff global_step / decay_step > count[row], and its count is then   */
+/*    incremented; w -= (lr g) / sqrt(accum).                                 */
+/*  DR_OPT_ADAM -- adam.py's _apply_sparse_shared (non-lazy sparse Adam).      */
+/*    slot1 = m, slot2 = v, powers = device {beta1_power, beta2_power}, read  */
+/*    and NOT advanced (they are the optimizer's, advanced once per step by   */
+/*    the caller); alpha = lr sqrt(1 - beta2_power) / (1 - beta1_power) is    */
+/*    formed on the device.  A named row: m = m beta1 + g (1 - beta1), v = v  */
+/*    beta2 + (g g)(1 - beta2), w -= (m alpha) / (sqrt(v) + epsilon)          */
+/*    (DR_OPT_ADAM_ASYNC's element).  EVERY OTHER ROW of the table: m = m     */
+/*    beta1, v = v beta2, w -= (m alpha) / (sqrt(v) + epsilon) -- nothing is  */
+/*    added, a -0.0 m keeps its sign.  Once per call, also when N == 0: a     */
+/*    table that is in the call steps.  The workspace holds one bit per row   */
+/*    of a launch group's tables for this (hence the optimizer argument of    */
+/*    the size entry); every row is read and written once.                    */
+/* Refused with DR_INVALID_ARGUMENT before any launch, besides what           */
+/* dr_dense_apply_grouped refuses: an unknown code, NULL opts for FTRL or     */
+/* AdagradDecay, a missing slot1 / slot2 for the three, missing powers for    */
+/* Adam, a misaligned count, decay_step <= 0, lr == 0 for FTRL.               */
+typedef struct {
+  float l1, l2, lr_power, l2_shrinkage;   /* DR_OPT_FTRL                      */
+  float decay_rate, decay_baseline;       /* DR_OPT_ADAGRAD_DECAY             */
+  int64_t decay_step, global_step;
+} dr_dense_apply_opts;
+size_t dr_dense_apply_grouped_ex_workspace_size(int optimizer,
+                                                const dr_dense_apply_desc* descs_host,
+                                                int num_tables);
+int dr_dense_apply_grouped_ex(int optimizer, const dr_dense_apply_desc* descs_host,
+                              int num_tables, float lr, float beta1, float beta2, float epsilon,
+                              const dr_dense_apply_opts* opts, void* ws, size_t ws_bytes,
+                              void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Adaptive embedding (AdaptiveEmbeddingVariable): an id whose mask is set   */

@@ -26,8 +26,18 @@ Last, the cost of long runs (one lane group walks a run): one table, 65 536
 positions, apply_gradients alone, for uniformly random rows, 128 runs of 512
 and every position on one row; the two engine arms, the same rounds.
 
+--opt adam | ftrl | adagrad_decay | all measures the
+optimizers of dr_dense_apply_grouped_ex instead, with the same method:
+apply_gradients alone over 8 DenseTables of [3 536, 128] with 65 536 positions
+each (section 21's shape), native against the torch arm, after one step of
+both arms from equal tables is checked against tests/dense_opt_ref.py (native
+bit for bit; FTRL here has lr_power -0.5).  With adam also one table of
+[2^20, 128] with 65 536 positions, where the sweep over the unnamed rows
+dominates; --sweep-only N runs just N native steps of that (for a kernel
+trace of its own) and prints the bytes the sweep moves per call.
+
 usage: python tools/dense_apply_ab.py [--features 4] [--rounds 5] [--reps 20]
-           [--out profiles/dense_apply.json]"""
+           [--opt adagrad] [--sweep-only 0] [--out profiles/dense_apply.json]"""
 import argparse
 import json
 import os
@@ -85,13 +95,148 @@ def _order(names, r):
     return names
 
 
+BIG_ROWS = 1 << 20
+EX_OPTS = ("adam", "ftrl", "adagrad_decay")
+
+
+def _ex_optimizer(dr, name):
+    if name == "adam":
+        return dr.AdamOptimizer(LR)
+    if name == "ftrl":
+        return dr.FtrlOptimizer(LR, l1_regularization_strength=0.001,
+                                l2_regularization_strength=0.001)
+    return dr.AdagradDecayOptimizer(LR, global_step=0, accumulator_decay_step=1)
+
+
+def _ex_reference(orc, name, w, idx, val):
+    """One first step of a fresh optimizer of _ex_optimizer on table w."""
+    import dense_opt_ref as ref
+    if name == "adam":
+        ref.adam(orc, w, np.zeros_like(w), np.zeros_like(w), idx, val, LR, 0.9, 0.999, 1e-8,
+                 0.9, 0.999)
+    elif name == "ftrl":
+        ref.ftrl(orc, w, np.full_like(w, 0.1), np.zeros_like(w), idx, val, LR, 0.001, 0.001,
+                 -0.5, 0.0)
+    else:
+        ref.adagrad_decay(orc, w, np.full_like(w, 0.1), np.zeros(w.shape[0], np.int64), idx, val,
+                          LR, 1, 0.9, 0.1, 1)
+    return w
+
+
+def _ex_arms(dr, training, name, tables, idxs, vals):
+    """{arm: call} -- one apply_gradients over copies of `tables`, each with
+    its slice queued again."""
+    calls, state = {}, {}
+    for arm in ARMS[:2]:
+        tabs = [dr.DenseTable(t.clone()) for t in tables]
+        opt = _ex_optimizer(dr, name)
+        state[arm] = tabs
+
+        def call(arm=arm, tabs=tabs, opt=opt):
+            for tab, i, v in zip(tabs, idxs, vals):
+                tab.pending_grads.append(dr.IndexedSlices(v, i))
+            training._NATIVE_DENSE = arm == "native"
+            try:
+                opt.apply_gradients(tabs)
+            finally:
+                training._NATIVE_DENSE = True
+        calls[arm] = call
+    return calls, state
+
+
+def main_ex(args):
+    import deeprec_amd as dr
+    from deeprec_amd import training
+    from oracle import oracle as orc
+    orc.build()
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    names = EX_OPTS if args.opt == "all" else (args.opt,)
+    T = 2 * args.features
+    res, checks = {}, {}
+    if not args.sweep_only:
+        tables = [torch.randn((QR, DIM), generator=g, device=dev) * 0.05 for _ in range(T)]
+        idxs = [torch.randint(0, QR, (ONEHOT,), generator=g, device=dev) for _ in range(T)]
+        vals = [torch.randn((ONEHOT, DIM), generator=g, device=dev) * 0.01 for _ in range(T)]
+        for name in names:
+            calls, state = _ex_arms(dr, training, name, tables, idxs, vals)
+            for arm in calls:
+                calls[arm]()                       # the checked step (and the warm-up)
+            dr.status_check()
+            diff = 0
+            for k in range(T):
+                want = _ex_reference(orc, name, tables[k].cpu().numpy().copy(),
+                                     idxs[k].cpu().numpy(), vals[k].cpu().numpy())
+                got = state["native"][k].weight.cpu().numpy()
+                assert np.array_equal(got.view(np.int32), want.view(np.int32)), (name, k)
+                got_t = state["torch"][k].weight.cpu().numpy()
+                np.testing.assert_allclose(got_t, want, rtol=1e-5, atol=1e-6)
+                diff += int((got_t.view(np.int32) != want.view(np.int32)).sum())
+            checks[name] = {"native == reference (bits)": True,
+                            "torch arm elements differing from the reference in bits": diff,
+                            "elements": T * QR * DIM}
+            for r in range(args.rounds):
+                for arm in _order(ARMS[:2], r):
+                    res.setdefault("%s: apply_gradients alone, %d tables x %d positions, %s ms"
+                                   % (name, T, ONEHOT, arm), []).append(
+                        _clock(calls[arm], args.reps))
+            del calls, state
+            torch.cuda.empty_cache()
+            print("%s done" % name, flush=True)
+    extra = {}
+    if "adam" in names:
+        table = torch.randn((BIG_ROWS, DIM), generator=g, device=dev) * 0.05
+        idx = torch.randint(0, BIG_ROWS, (ONEHOT,), generator=g, device=dev)
+        val = torch.randn((ONEHOT, DIM), generator=g, device=dev) * 0.01
+        unnamed = BIG_ROWS - int(torch.unique(idx).numel())
+        # what the sweep moves: w, m, v of every row read, of every unnamed row written
+        extra = {"big table rows": BIG_ROWS, "unnamed rows": unnamed,
+                 "sweep bytes per call": (3 * BIG_ROWS + 3 * unnamed) * DIM * 4,
+                 "six full row passes bytes": 6 * BIG_ROWS * DIM * 4}
+        calls, _ = _ex_arms(dr, training, "adam", [table], [idx], [val])
+        del table
+        if args.sweep_only:
+            for _ in range(args.sweep_only + 2):
+                calls["native"]()
+            torch.cuda.synchronize()
+            dr.status_check()
+            print(json.dumps(extra, sort_keys=True))
+            return
+        for arm in calls:
+            calls[arm]()                           # warm-up
+        for r in range(args.rounds):
+            for arm in _order(ARMS[:2], r):
+                res.setdefault("adam: apply_gradients alone, 1 table of %d rows x %d positions, "
+                               "%s ms" % (BIG_ROWS, ONEHOT, arm), []).append(
+                    _clock(calls[arm], max(1, args.reps // 4)))
+    results = {k: _summary(v) for k, v in sorted(res.items())}
+    out = {"tables": T, "dim": DIM, "rows": QR, "positions": ONEHOT, "rounds": args.rounds,
+           "reps": args.reps, "device": torch.cuda.get_device_name(0),
+           "checked before timing": checks, "results": results, "adam sweep case": extra}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({"results": results, "checks": checks, "adam sweep case": extra}, indent=1,
+                     sort_keys=True))
+    dr.status_check()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--features", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dense_apply.json"))
+    ap.add_argument("--opt", default="adagrad", choices=("adagrad", "all") + EX_OPTS)
+    ap.add_argument("--sweep-only", type=int, default=0)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "dense_apply.json" if args.opt == "adagrad"
+                                else "dense_apply_opts.json")
+    if args.opt != "adagrad":
+        return main_ex(args)
     import deeprec_amd as dr
     from deeprec_amd import training
     from oracle import oracle as orc
