@@ -21,7 +21,7 @@ from .kv_variable_ops import (AdaptiveEmbeddingVariable, CBFFilter, CounterFilte
                               StorageType, flush_releases, get_adaptive_embedding_variable,
                               get_embedding_variable,
                               get_multihash_variable, read_only_lookups, read_only_serves_tier)
-from .ops import set_validate, status_check
+from .ops import gru_sequence, set_validate, status_check
 from .string_ops import StringTensor, string_to_hash_bucket_fast
 from .training import (AdagradDecayOptimizer, AdagradOptimizer, AdamAsyncOptimizer, AdamOptimizer,
                        FtrlOptimizer, GradientDescentOptimizer)
@@ -37,5 +37,5 @@ __all__ = [
     "string_to_hash_bucket_fast", "StorageOption", "StorageType", "InitializerOption",
     "read_only_serves_tier", "MultiHashVariable", "MultiHashVariableConfig",
     "get_multihash_variable", "AdaptiveEmbeddingVariable", "get_adaptive_embedding_variable",
-    "adaptive_embedding_lookup_sparse",
+    "adaptive_embedding_lookup_sparse", "gru_sequence",
 ]

@@ -442,6 +442,9 @@ SIGNATURES = {
     "dr_din_mlp_wgrad": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _SZ, _P]),
     "dr_din_mlp_wgrad_valid": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _P, _P,
                                       _SZ, _P]),
+    "dr_gru_seq_saved_size": (_SZ, [_I64, _I64, _I64]),
+    "dr_gru_seq_forward": (_I32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "dr_gru_seq_backward": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
     "dr_fingerprint64": (_I32, [_P, _P, _I64, _P, _P]),
     "dr_string_to_hash_bucket_fast": (_I32, [_P, _P, _I64, _I64, _P, _P]),
     "dr_crc32c_extend": (C.c_uint32, [C.c_uint32, _P, _SZ]),

@@ -18,6 +18,8 @@ north_star asks.
   DNN over the concatenated embeddings, final DNN over [dnn, linear, fm],
   a last 1-unit layer, sigmoid.
 * DIN: modelzoo/DIN/script/model.py:11-150,368-392 (DIN class below).
+* DIEN: DIN's sibling with the interest-evolution layer (GRU + attention-
+  gated GRU, csrc/gru.hip) and the auxiliary loss (DIEN class below).
 * WDL: modelzoo/WDL/train.py:182-335 (WDL class below).
 * DCN-v2: stacked cross network on the MFMA kernel (DCNv2 class below).
 
@@ -1157,6 +1159,201 @@ def din_train_step(model, batch, dense_opt, ev_opt, global_step=None, world=1, g
     uids, mids, cats, mid_his, cat_his, mask, target = batch
     y_hat = model(uids, mids, cats, mid_his, cat_his, mask)
     loss = -(torch.log(y_hat) * target).mean()
+    dense_opt.zero_grad(set_to_none=True)
+    if world > 1:
+        (loss / world).backward()
+        allreduce_dense_grads(list(model.parameters()), group=group, staged=staged)
+        from .sharded import sync_replicated_grads
+        sync_replicated_grads(list(model.evs), group=group, staged=staged)
+    else:
+        loss.backward()
+    dense_opt.step()
+    ev_opt.apply_gradients(model.evs, global_step=global_step)
+    return loss
+
+
+class _DinMlpScoresFn(torch.autograd.Function):
+    """The attention MLP's scores alone (dr_din_mlp_forward / _backward,
+    din_all never formed): DIEN's din_fcn_attention in mode LIST keeps the
+    softmax weights, not the weighted sum, so the pool kernels do not apply."""
+
+    @staticmethod
+    def forward(ctx, query, facts, mask, w1, b1, w2, b2, w3, b3):
+        scores, buf = ops.din_mlp_forward(query, facts, mask, w1, b1, w2, b2, w3, b3)
+        ctx.save_for_backward(query, facts, w1, w3)
+        ctx.buf = buf
+        return scores
+
+    @staticmethod
+    def backward(ctx, g_scores):
+        query, facts, w1, w3 = ctx.saved_tensors
+        gf = torch.zeros_like(facts, dtype=torch.float32)
+        gq, dW1, db1, dW2, db2, dw3, db3 = ops.din_mlp_backward(query, facts, w1, w3, ctx.buf,
+                                                                 g_scores, gf)
+        ctx.buf = None
+        return gq, gf, None, dW1, db1, dW2, db2, dw3, db3
+
+
+class _HostTableLookupFn(torch.autograd.Function):
+    """CPU form of the merged one-hot lookup over dense tables (objects with
+    .weight [rows, dim] and .pending_grads, e.g. DenseTable): ids [T, N] ->
+    [N, sum dim]; the backward queues one IndexedSlices per table on its
+    pending_grads, rows in the order of ids."""
+
+    @staticmethod
+    def forward(ctx, anchor, tables, ids):
+        ctx.tables, ctx.ids = tables, ids
+        return torch.cat([t.weight[ids[i]] for i, t in enumerate(tables)], 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        from .kv_variable_ops import IndexedSlices
+        col = 0
+        for i, t in enumerate(ctx.tables):
+            t.pending_grads.append(IndexedSlices(g[:, col:col + t.dim].contiguous(), ctx.ids[i]))
+            col += t.dim
+        return None, None, None
+
+
+class GruLayer(torch.nn.Module):
+    """dynamic_rnn over TF's GRUCell (att None) or DIEN's VecAttGRUCell (att
+    [B, T]) with TF's variables: gates/kernel [I + H, 2H] and candidate/kernel
+    [I + H, H] (Glorot uniform), gates/bias 1, candidate/bias 0.  The input
+    part x W_x + b is one GEMM over all positions; the recurrence is
+    ops.gru_sequence (one HIP kernel each way on the GPU)."""
+
+    def __init__(self, n_in, hidden):
+        super().__init__()
+        self.n_in, self.hidden = n_in, hidden
+        self.gates_kernel = torch.nn.Parameter(torch.empty(n_in + hidden, 2 * hidden))
+        self.gates_bias = torch.nn.Parameter(torch.ones(2 * hidden))
+        self.candidate_kernel = torch.nn.Parameter(torch.empty(n_in + hidden, hidden))
+        self.candidate_bias = torch.nn.Parameter(torch.zeros(hidden))
+        torch.nn.init.xavier_uniform_(self.gates_kernel)
+        torch.nn.init.xavier_uniform_(self.candidate_kernel)
+
+    def forward(self, x, seq_len, att=None):
+        n = self.n_in
+        w_x = torch.cat([self.gates_kernel[:n], self.candidate_kernel[:n]], 1)
+        xp = x @ w_x + torch.cat([self.gates_bias, self.candidate_bias])
+        return ops.gru_sequence(xp, self.gates_kernel[n:], self.candidate_kernel[n:], seq_len, att)
+
+
+class DIEN(torch.nn.Module):
+    """modelzoo/DIEN/script/model.py Model_DIN_V2_Gru_Vec_attGru_Neg on EVs:
+    DIN's embedding layer plus the first negative sample of every history
+    position (noclk_mid_his / noclk_cat_his [B, T], the reference's
+    noclk_*_batch_embedded[:, :, 0, :]); rnn_1 = dynamic_rnn(GRUCell(2D)) over
+    the history; the auxiliary loss on its outputs; din_fcn_attention (the
+    DIN attention MLP on (item_eb, rnn_outputs), softmax over T, mode LIST)
+    -> alphas; rnn_2 = dynamic_rnn(VecAttGRUCell(2D)) with alphas, whose final
+    state joins DIN's FCN head in the place of the attention output.
+    forward returns (y_hat [B, 2], aux_loss).
+
+    On CPU tensors the three variables are dense tables (objects with
+    .weight, .dim and .pending_grads, e.g. DenseTable); every kernel then
+    takes its torch composition."""
+
+    def __init__(self, uid_ev, mid_ev, cat_ev):
+        super().__init__()
+        self.uid_ev, self.mid_ev, self.cat_ev = uid_ev, mid_ev, cat_ev
+        self.evs = [uid_ev, mid_ev, cat_ev]
+        H = 2 * mid_ev.dim
+        self.gru1 = GruLayer(H, H)
+        self.gru2 = GruLayer(H, H)
+        self.f1_att = SplitKLinear(4 * H, 80)
+        self.f2_att = SplitKLinear(80, 40)
+        self.f3_att = SplitKLinear(40, 1)
+        self.aux_bn_gamma = torch.nn.Parameter(torch.ones(2 * H))
+        self.aux_bn_beta = torch.nn.Parameter(torch.zeros(2 * H))
+        self.aux_f1 = SplitKLinear(2 * H, 100)
+        self.aux_f2 = SplitKLinear(100, 50)
+        self.aux_f3 = SplitKLinear(50, 2)
+        n_in = uid_ev.dim + 4 * H
+        self.bn1_gamma = torch.nn.Parameter(torch.ones(n_in))
+        self.bn1_beta = torch.nn.Parameter(torch.zeros(n_in))
+        self.dnn1 = torch.nn.Linear(n_in, 200)
+        self.dice_1 = Dice(200)
+        self.dnn2 = torch.nn.Linear(200, 80)
+        self.dice_2 = Dice(80)
+        self.dnn3 = torch.nn.Linear(80, 2)
+        self.uid_lookup = _OneHotLookup([uid_ev])
+        self.item_lookup = _OneHotLookup([mid_ev, cat_ev])
+
+    BN_SCALE = 1.0 / (1.0 + 1e-3) ** 0.5   # moving variance 1, epsilon 1e-3
+    PAD = float(-2 ** 32 + 1)
+
+    def _lookup(self, lookup, ids):
+        if ids.is_cuda:
+            return lookup(ids)
+        anchor = self.bn1_beta      # makes the node differentiable: the tables are not tensors
+        return _HostTableLookupFn.apply(anchor, lookup.evs, ids)
+
+    def _scores(self, item_eb, facts, mask):
+        B, T, H = facts.shape
+        if DIN.fused_attention and facts.is_cuda and H in ops.DIN_MLP_HIDDEN:
+            return _DinMlpScoresFn.apply(item_eb, facts.contiguous(), mask, self.f1_att.weight,
+                                         self.f1_att.bias, self.f2_att.weight, self.f2_att.bias,
+                                         self.f3_att.weight, self.f3_att.bias)
+        q = item_eb.unsqueeze(1).expand(-1, T, -1)
+        h = torch.sigmoid(self.f1_att(torch.cat([q, facts, q - facts, q * facts], -1)))
+        h = torch.sigmoid(self.f2_att(h))
+        return self.f3_att(h).view(B, T)
+
+    def _aux_prob(self, h_states, seq):
+        x = torch.cat([h_states, seq], -1) * self.BN_SCALE * self.aux_bn_gamma + self.aux_bn_beta
+        x = torch.sigmoid(self.aux_f1(x))
+        x = torch.sigmoid(self.aux_f2(x))
+        return (torch.softmax(self.aux_f3(x), -1) + 1e-8)[..., 0]
+
+    def auxiliary_loss(self, h_states, click_seq, noclick_seq, mask):
+        if h_states.shape[1] == 0:
+            return h_states.new_zeros(())
+        click = self._aux_prob(h_states, click_seq)
+        noclick = self._aux_prob(h_states, noclick_seq)
+        return ((-torch.log(click) - torch.log(1.0 - noclick)) * mask).mean()
+
+    def forward(self, uids, mids, cats, mid_his, cat_his, mask, noclk_mid_his, noclk_cat_his):
+        B, T = mid_his.shape
+        uid_e = self._lookup(self.uid_lookup, uids.reshape(1, B))
+        # one lookup of the mid / cat EVs over [target | history | noclk history]:
+        # each EV gets one gradient whose per-id sums are single chains in that order
+        ids = torch.stack([torch.cat([mids, mid_his.reshape(-1), noclk_mid_his.reshape(-1)]),
+                           torch.cat([cats, cat_his.reshape(-1), noclk_cat_his.reshape(-1)])])
+        allv = self._lookup(self.item_lookup, ids)                                 # [B + 2 B T, 2D]
+        item_eb = allv[:B]
+        item_his_eb = allv[B:B + B * T].view(B, T, -1)
+        noclk_his_eb = allv[B + B * T:].view(B, T, -1)
+        his_sum = item_his_eb.sum(1)
+        seq_len = mask.sum(1).to(torch.int32)
+        rnn_outputs, _ = self.gru1(item_his_eb, seq_len)
+        aux = self.auxiliary_loss(rnn_outputs[:, :-1], item_his_eb[:, 1:], noclk_his_eb[:, 1:],
+                                  mask[:, 1:])
+        scores = self._scores(item_eb, rnn_outputs, mask)
+        alphas = torch.softmax(torch.where(mask == 1, scores, torch.full_like(scores, self.PAD)),
+                               -1)
+        _, final_state2 = self.gru2(rnn_outputs, seq_len, alphas)
+        if DIN.fused_fcn_input and item_eb.is_cuda and item_eb.dtype == torch.float32:
+            bn = _DinFcnInputFn.apply(uid_e, item_eb, his_sum, final_state2, self.bn1_gamma,
+                                      self.bn1_beta, self.BN_SCALE)
+        else:
+            inp = torch.cat([uid_e, item_eb, his_sum, item_eb * his_sum, final_state2], -1)
+            bn = inp * self.BN_SCALE * self.bn1_gamma + self.bn1_beta
+        x = self.dice_1(self.dnn1(bn))
+        x = self.dice_2(self.dnn2(x))
+        return torch.softmax(self.dnn3(x), -1) + 1e-8, aux
+
+
+def dien_train_step(model, batch, dense_opt, ev_opt, global_step=None, world=1, group=None,
+                    staged=False):
+    """One DIEN step: loss = ctr_loss + aux_loss (model.py: -mean(log(y_hat) *
+    target) plus the auxiliary loss), backward, dense optimizer, KV optimizer
+    on the uid / mid / cat EVs; world > 1 as din_train_step (data parallel
+    over replicated EVs).  batch = (uids, mids, cats, mid_his, cat_his, mask,
+    noclk_mid_his, noclk_cat_his, target)."""
+    target = batch[-1]
+    y_hat, aux = model(*batch[:-1])
+    loss = -(torch.log(y_hat) * target).mean() + aux
     dense_opt.zero_grad(set_to_none=True)
     if world > 1:
         (loss / world).backward()

@@ -1084,6 +1084,126 @@ def din_attention_pool_grad(alphas, mask, facts, grad_att, grad_sum=None, out=No
 
 
 # ---------------------------------------------------------------------------
+# GRU / attention-gated GRU over a padded sequence (DIEN's interest layers:
+# dynamic_rnn(GRUCell) and dynamic_rnn(VecAttGRUCell))
+# ---------------------------------------------------------------------------
+GRU_MAX_HIDDEN = 64
+# DR_GRU=torch: the torch composition of the same contract on the GPU too (A/B)
+_GRU_NATIVE = os.environ.get("DR_GRU", "native") != "torch"
+
+
+def gru_native_ok(xp):
+    """The kernels take this input: fp32 on a GPU, H a multiple of 4 in [4, 64]."""
+    H = xp.shape[2] // 3
+    return (xp.is_cuda and xp.dtype == torch.float32 and xp.shape[0] >= 1 and xp.shape[1] >= 1
+            and H % 4 == 0 and 4 <= H <= GRU_MAX_HIDDEN)
+
+
+def gru_seq_forward(xp, wh_g, wh_c, seq_len, att=None):
+    """dr_gru_seq_forward: xp [B, T, 3H] (x W_x + b; columns r | u | c), wh_g
+    [H, 2H], wh_c [H, H], seq_len [B], att [B, T] or None -> (out [B, T, H],
+    h_final [B, H], saved [B, T, 3H] = r | u | c per valid step, zeros after)."""
+    dev = _dev(xp)
+    B, T, H3 = xp.shape
+    H = H3 // 3
+    x, wg, wc = _c(xp, torch.float32), _c(wh_g, torch.float32), _c(wh_c, torch.float32)
+    sl = _c(seq_len, torch.int32)
+    a = None if att is None else _c(att, torch.float32)
+    e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+    out, hf = e(B, T, H), e(B, H)
+    saved = e(lib().dr_gru_seq_saved_size(B, T, H) // 4).view(B, T, H3)
+    check(lib().dr_gru_seq_forward(ptr(x), ptr(wg), ptr(wc), ptr(sl), ptr(a), B, T, H, ptr(out),
+                                   ptr(hf), ptr(saved), stream_handle(dev)))
+    _post(dev)
+    return out, hf, saved
+
+
+def gru_seq_backward(wh_g, wh_c, seq_len, att, out, saved, grad_out, grad_h_final,
+                     need_grad_att=True):
+    """dr_gru_seq_backward -> (grad_xp [B, T, 3H], grad_att [B, T] or None);
+    grad_out / grad_h_final may be None (zeros)."""
+    dev = _dev(out)
+    B, T, H = out.shape
+    wg, wc = _c(wh_g, torch.float32), _c(wh_c, torch.float32)
+    sl = _c(seq_len, torch.int32)
+    a = None if att is None else _c(att, torch.float32)
+    go = None if grad_out is None else _c(grad_out, torch.float32)
+    gh = None if grad_h_final is None else _c(grad_h_final, torch.float32)
+    gxp = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
+    ga = (torch.empty((B, T), dtype=torch.float32, device=dev)
+          if a is not None and need_grad_att else None)
+    check(lib().dr_gru_seq_backward(ptr(wg), ptr(wc), ptr(sl), ptr(a), ptr(_c(out, torch.float32)),
+                                    ptr(_c(saved, torch.float32)), ptr(go), ptr(gh), B, T, H,
+                                    ptr(gxp), ptr(ga), stream_handle(dev)))
+    _post(dev)
+    return gxp, ga
+
+
+class _GruSequenceFn(torch.autograd.Function):
+    """One launch each way (dr_gru_seq_forward / _backward); the state-weight
+    gradients are two GEMMs over what the kernels leave."""
+
+    @staticmethod
+    def forward(ctx, xp, wh_g, wh_c, seq_len, att):
+        out, hf, saved = gru_seq_forward(xp, wh_g, wh_c, seq_len, att)
+        ctx.save_for_backward(wh_g, wh_c, seq_len, att, out, saved)
+        return out, hf
+
+    @staticmethod
+    def backward(ctx, g_out, g_hf):
+        wh_g, wh_c, seq_len, att, out, saved = ctx.saved_tensors
+        B, T, H = out.shape
+        need_att = att is not None and ctx.needs_input_grad[4]
+        gxp, ga = gru_seq_backward(wh_g, wh_c, seq_len, att, out, saved, g_out, g_hf, need_att)
+        dwg = dwc = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            hp = torch.zeros_like(out)
+            hp[:, 1:] = out[:, :-1]
+            hp = hp.view(B * T, H)
+            g2 = gxp.view(B * T, 3 * H)
+            dwg = hp.t() @ g2[:, :2 * H]
+            dwc = (saved.view(B * T, 3 * H)[:, :H] * hp).t() @ g2[:, 2 * H:]
+        return gxp, dwg, dwc, None, ga
+
+
+def _gru_sequence_torch(xp, wh_g, wh_c, seq_len, att=None):
+    """The contract of dr_gru_seq_forward as a torch composition (autograd
+    forms the backward): CPU tensors, widths outside the kernels' set, and
+    the DR_GRU=torch arm."""
+    B, T, H3 = xp.shape
+    H = H3 // 3
+    h = xp.new_zeros(B, H)
+    lens = seq_len.to(xp.device).reshape(B, 1)
+    outs = []
+    for t in range(T):
+        x = xp[:, t]
+        g = torch.sigmoid(x[:, :2 * H] + h @ wh_g)
+        r, u = g[:, :H], g[:, H:]
+        c = torch.tanh(x[:, 2 * H:] + (r * h) @ wh_c)
+        if att is not None:
+            u = (1.0 - att[:, t:t + 1]) * u
+        nh = u * h + (1.0 - u) * c
+        live = t < lens
+        outs.append(torch.where(live, nh, torch.zeros_like(nh)))
+        h = torch.where(live, nh, h)
+    return torch.stack(outs, 1), h
+
+
+def gru_sequence(xp, wh_g, wh_c, seq_len, att=None):
+    """GRU (att None) or attention-gated GRU (AUGRU) over a padded sequence
+    with dynamic_rnn(sequence_length=seq_len) semantics -> (out [B, T, H],
+    h_final [B, H]); gradients for xp, wh_g, wh_c and att.  xp [B, T, 3H] is
+    x W_x + b with columns r | u | c; TF's cell: c = tanh(xp_c + (r h) wh_c).
+    fp32 GPU tensors with H a multiple of 4 up to 64 run one HIP kernel each
+    way; anything else (and DR_GRU=torch) the torch composition."""
+    if xp.dim() != 3 or xp.shape[2] % 3:
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT, "gru_sequence: xp must be [B, T, 3H]")
+    if _GRU_NATIVE and gru_native_ok(xp):
+        return _GruSequenceFn.apply(xp, wh_g, wh_c, seq_len, att)
+    return _gru_sequence_torch(xp, wh_g, wh_c, seq_len, att)
+
+
+# ---------------------------------------------------------------------------
 # Row-sharded exchange helpers
 # ---------------------------------------------------------------------------
 def partition_by_owner(keys, world, n_dev=None):

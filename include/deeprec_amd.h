@@ -1705,6 +1705,41 @@ int dr_din_fcn_input_backward(const float* grad, const float* uid, const float* 
                               float* g_beta, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* GRU and attention-gated GRU (AUGRU, VecAttGRUCell) over a padded          */
+/* sequence, dynamic_rnn(sequence_length) semantics, fp32 (DESIGN section    */
+/* 25).  TF's GRUCell: the reset gate is applied before the candidate        */
+/* product.  xp [B, T, 3H] = x W_x + b (columns r | u | c), wh_g [H, 2H] and  */
+/* wh_c [H, H] the state rows of gates/kernel and candidate/kernel,          */
+/* seq_len [B] int32 (clamped to [0, T]), att [B, T] or NULL (plain GRU).    */
+/* For t < seq_len[b], from h = 0:                                           */
+/*   [r, u] = sigmoid(xp[0:2H] + h wh_g);  c = tanh(xp[2H:3H] + (r h) wh_c)  */
+/*   u' = (1 - att) u;  h = u' h + (1 - u') c;  out[b, t] = h                */
+/* out [B, T, H] is 0 at t >= seq_len[b]; h_final [B, H] is the state after  */
+/* the last valid step (0 for an empty row); saved [B, T, 3H] (r | u | c,    */
+/* zeros at padded steps; dr_gru_seq_saved_size bytes) is for the backward.  */
+/* One launch; no allocation, host read or synchronisation.  H a multiple of */
+/* 4 in [4, 64], T >= 1, B >= 0 (B == 0: nothing is launched); xp, saved and */
+/* grad_xp 16-byte aligned; anything else is DR_INVALID_ARGUMENT.  A row's   */
+/* result does not depend on the rows around it or on T.                     */
+/* ------------------------------------------------------------------------ */
+size_t dr_gru_seq_saved_size(int64_t batch, int64_t seq_len, int64_t hidden);
+int dr_gru_seq_forward(const float* xp, const float* wh_g, const float* wh_c,
+                       const int32_t* seq_len, const float* att /* nullable */, int64_t batch,
+                       int64_t max_len, int64_t hidden, float* out, float* h_final, float* saved,
+                       void* stream);
+/* Its backward from grad_out [B, T, H] and grad_h_final [B, H] (each         */
+/* nullable = zeros): grad_xp [B, T, 3H] = [d pre-r | d pre-u | d pre-c] and, */
+/* with att, grad_att [B, T] (nullable; refused without att), both exactly 0  */
+/* at t >= seq_len[b].  The state-weight gradients are the caller's GEMMs:   */
+/* d wh_g = h_prev^T grad_xp[:, 0:2H], d wh_c = (r h_prev)^T grad_xp[:, 2H:], */
+/* h_prev[b, t] = out[b, t - 1] (0 at t = 0), r = saved[:, 0:H].             */
+int dr_gru_seq_backward(const float* wh_g, const float* wh_c, const int32_t* seq_len,
+                        const float* att /* nullable */, const float* out, const float* saved,
+                        const float* grad_out, const float* grad_h_final, int64_t batch,
+                        int64_t max_len, int64_t hidden, float* grad_xp, float* grad_att,
+                        void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* String -> id, the step before the lookup.  Strings are one byte buffer    */
 /* plus int64 offsets[n+1] (string i = bytes[offsets[i] .. offsets[i+1])).   */
 /* ------------------------------------------------------------------------ */

@@ -3,11 +3,13 @@ DLRM (modelzoo/DLRM/train.py), DeepFM (modelzoo/DeepFM/train.py) or DCN-v2
 (configs[4], 3 bf16 cross layers + deep MLP) forward,
 BCE loss, backward, dense SGD, KV SGD / Adagrad on every EV; or DIN
 (modelzoo/DIN, BASELINE configs[3]: uid / item / category EVs of dim 18,
-history lengths U[1, maxlen], Adam as in the reference).  Prints one JSON
+history lengths U[1, maxlen], Adam as in the reference) or DIEN (the same
+shape plus one negative sample per history position; DR_GRU=torch runs its
+GRUs as torch compositions, the A/B arm).  Prints one JSON
 line with samples/s and the per-phase split.  A measurement aid for
 SURVEY 8f #4; bench.py's headline metric is the forward lookup.
 
-  python tools/model_step.py [--model dlrm|deepfm|din|dcn|wdl] [--rows 12500000] [--dim 128]
+  python tools/model_step.py [--model dlrm|deepfm|din|dien|dcn|wdl] [--rows 12500000] [--dim 128]
 """
 import argparse
 import json
@@ -23,7 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "deeprec-1_amd"))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="dlrm", choices=["dlrm", "deepfm", "din", "dcn", "wdl"])
+    ap.add_argument("--model", default="dlrm", choices=["dlrm", "deepfm", "din", "dien", "dcn", "wdl"])
     ap.add_argument("--maxlen", type=int, default=100, help="DIN history length bound")
     ap.add_argument("--tables", type=int, default=26)
     ap.add_argument("--rows", type=int, default=12_500_000)
@@ -38,7 +40,7 @@ def main():
     from deeprec_amd import modelzoo as mz
     dr.load()
     dev = torch.device("cuda", 0)
-    if args.model == "din":
+    if args.model in ("din", "dien"):
         args.batch = args.batch or 4096
         return din(args, dr, mz, dev)
     if args.model == "wdl":
@@ -143,7 +145,9 @@ def wdl(args, dr, mz, dev):
 def din(args, dr, mz, dev):
     """DIN step: B samples, history lengths U[1, maxlen] padded to the batch
     max (prepare_data, modelzoo/DIN/train.py:24-88), vocab 5e5 users / 4e5
-    items / 2e3 categories, dim 18, Adam."""
+    items / 2e3 categories, dim 18, Adam.  DIEN: the
+    same batch plus one negative item / category per history position."""
+    dien = args.model == "dien"
     B, T, D = args.batch, args.maxlen, 18
     R = (500_000, 400_000, 2_000)
     evs = []
@@ -151,7 +155,8 @@ def din(args, dr, mz, dev):
         ev = dr.EmbeddingVariable("din%d" % i, D, 0.0, capacity=r + (1 << 16), device=dev)
         ev.insert_synthetic(0, r, seed=700 + i)
         evs.append(ev)
-    model = mz.DIN(*evs).to(dev)
+    model = (mz.DIEN if dien else mz.DIN)(*evs).to(dev)
+    step = mz.dien_train_step if dien else mz.din_train_step
     dopt = torch.optim.Adam(model.parameters(), lr=0.001)
     eopt = dr.AdamOptimizer(0.001)
     g = torch.Generator(device=dev)
@@ -164,25 +169,32 @@ def din(args, dr, mz, dev):
         mh = torch.randint(1, R[1], (B, Tb), generator=g, device=dev) * mask.long()
         ch = torch.randint(1, R[2], (B, Tb), generator=g, device=dev) * mask.long()
         lab = (torch.rand(B, generator=g, device=dev) > 0.5).long()
+        noclk = ()
+        if dien:
+            noclk = (torch.randint(1, R[1], (B, Tb), generator=g, device=dev) * mask.long(),
+                     torch.randint(1, R[2], (B, Tb), generator=g, device=dev) * mask.long())
         batches.append((torch.randint(0, R[0], (B,), generator=g, device=dev),
                         torch.randint(0, R[1], (B,), generator=g, device=dev),
-                        torch.randint(0, R[2], (B,), generator=g, device=dev), mh, ch, mask,
-                        torch.stack([lab, 1 - lab], 1).float()))
+                        torch.randint(0, R[2], (B,), generator=g, device=dev), mh, ch, mask)
+                       + noclk + (torch.stack([lab, 1 - lab], 1).float(),))
     for i in range(args.warmup):
-        mz.din_train_step(model, batches[i % 4], dopt, eopt, i)
+        step(model, batches[i % 4], dopt, eopt, i)
     torch.cuda.synchronize()
     print("[model_step] warmup ok", file=sys.stderr, flush=True)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = mz.din_train_step(model, batches[i % 4], dopt, eopt, i)
+        loss = step(model, batches[i % 4], dopt, eopt, i)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     dr.status_check(dev)
-    nnz = sum(int(b[5].numel()) * 2 + 3 * B for b in batches) / 4
-    print(json.dumps({"model": "din", "samples_per_s": round(B * args.steps / el, 1),
-                      "lookups_per_s": round(nnz * args.steps / el, 1),
-                      "ms_per_step": round(el / args.steps * 1e3, 3), "batch": B, "maxlen": T,
-                      "dim": D, "vocab": R, "opt": "adam", "loss": float(loss)}), flush=True)
+    nnz = sum(int(b[5].numel()) * (4 if dien else 2) + 3 * B for b in batches) / 4
+    res = {"model": args.model, "samples_per_s": round(B * args.steps / el, 1),
+           "lookups_per_s": round(nnz * args.steps / el, 1),
+           "ms_per_step": round(el / args.steps * 1e3, 3), "batch": B, "maxlen": T,
+           "dim": D, "vocab": R, "opt": "adam", "loss": float(loss)}
+    if dien:
+        res["gru"] = os.environ.get("DR_GRU", "native")
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
