@@ -20,6 +20,8 @@ north_star asks.
 * DIN: modelzoo/DIN/script/model.py:11-150,368-392 (DIN class below).
 * DIEN: DIN's sibling with the interest-evolution layer (GRU + attention-
   gated GRU, csrc/gru.hip) and the auxiliary loss (DIEN class below).
+* BST: the Behavior Sequence Transformer on DIN's inputs; its multi-head
+  self-attention is csrc/mha.hip (MultiHeadAttention and BST classes below).
 * WDL: modelzoo/WDL/train.py:182-335 (WDL class below).
 * DCN-v2: stacked cross network on the MFMA kernel (DCNv2 class below).
 
@@ -1365,6 +1367,91 @@ def dien_train_step(model, batch, dense_opt, ev_opt, global_step=None, world=1, 
     dense_opt.step()
     ev_opt.apply_gradients(model.evs, global_step=global_step)
     return loss
+
+
+def _normalize(x, gain, bias, eps=1e-8):
+    """The reference's normalize: layer norm over the last axis (biased
+    variance, epsilon inside the root), gain and bias."""
+    mean = x.mean(-1, keepdim=True)
+    var = ((x - mean) ** 2).mean(-1, keepdim=True)
+    return gain * (x - mean) / (var + eps) ** 0.5 + bias
+
+
+class MultiHeadAttention(torch.nn.Module):
+    """The reference's multihead_attention block on a padded history: one
+    packed relu(x [Wq | Wk | Wv] + b) projection, ops.multihead_attention on
+    its three column blocks (one HIP kernel each way on the GPU, no copy), a
+    residual (through a linear map when in_dim != num_units) and normalize."""
+
+    def __init__(self, in_dim, num_units=64, num_heads=4):
+        super().__init__()
+        self.num_units, self.num_heads = num_units, num_heads
+        self.qkv = torch.nn.Linear(in_dim, 3 * num_units)
+        self.res = torch.nn.Linear(in_dim, num_units) if in_dim != num_units else None
+        self.gain = torch.nn.Parameter(torch.ones(num_units))
+        self.bias = torch.nn.Parameter(torch.zeros(num_units))
+
+    def forward(self, x, seq_len):
+        E = self.num_units
+        p = torch.relu(self.qkv(x))                                               # [B, T, 3E]
+        out = ops.multihead_attention(p[..., :E], p[..., E:2 * E], p[..., 2 * E:], seq_len,
+                                      self.num_heads)
+        out = out + (x if self.res is None else self.res(x))
+        return _normalize(out, self.gain, self.bias)
+
+
+class BST(torch.nn.Module):
+    """Behavior Sequence Transformer (the reference zoo's BST) on DIN's inputs:
+    one merged item lookup over [target | history]; the sequence [target,
+    history...] plus a learned positional table; one MultiHeadAttention block
+    and a position-wise feed-forward (num_units -> 4 num_units -> num_units,
+    relu, residual, normalize); padded positions zeroed; the mean over the
+    valid positions joins [uid, item_eb] into the 200-80-2 head.  forward
+    returns y_hat [B, 2].  On CPU tensors the three variables are dense
+    tables, as for DIEN."""
+
+    def __init__(self, uid_ev, mid_ev, cat_ev, max_len=100, num_units=64, num_heads=4):
+        super().__init__()
+        self.uid_ev, self.mid_ev, self.cat_ev = uid_ev, mid_ev, cat_ev
+        self.evs = [uid_ev, mid_ev, cat_ev]
+        H = mid_ev.dim + cat_ev.dim
+        self.pos = torch.nn.Parameter(torch.randn(max_len + 1, H) * 0.01)
+        self.att = MultiHeadAttention(H, num_units, num_heads)
+        self.ffn1 = torch.nn.Linear(num_units, 4 * num_units)
+        self.ffn2 = torch.nn.Linear(4 * num_units, num_units)
+        self.ffn_gain = torch.nn.Parameter(torch.ones(num_units))
+        self.ffn_bias = torch.nn.Parameter(torch.zeros(num_units))
+        self.head = _mlp([uid_ev.dim + H + num_units, 200, 80, 2], last_act=False)
+        self.uid_lookup = _OneHotLookup([uid_ev])
+        self.item_lookup = _OneHotLookup([mid_ev, cat_ev])
+
+    def _lookup(self, lookup, ids):
+        if ids.is_cuda:
+            return lookup(ids)
+        return _HostTableLookupFn.apply(self.ffn_bias, lookup.evs, ids)
+
+    def forward(self, uids, mids, cats, mid_his, cat_his, mask):
+        B, T = mid_his.shape
+        uid_e = self._lookup(self.uid_lookup, uids.reshape(1, B))
+        ids = torch.stack([torch.cat([mids, mid_his.reshape(-1)]),
+                           torch.cat([cats, cat_his.reshape(-1)])])
+        allv = self._lookup(self.item_lookup, ids)                                 # [B + B T, H]
+        item_eb = allv[:B]
+        seq = torch.cat([item_eb.unsqueeze(1), allv[B:].view(B, T, -1)], 1) + self.pos[:T + 1]
+        seq_len = mask.sum(1).to(torch.int32) + 1          # the target leads: a valid prefix
+        x = self.att(seq, seq_len)
+        y = self.ffn2(torch.relu(self.ffn1(x))) + x
+        y = _normalize(y, self.ffn_gain, self.ffn_bias)
+        live = (torch.arange(T + 1, device=y.device)[None, :] < seq_len[:, None]).to(y.dtype)
+        pooled = (y * live.unsqueeze(-1)).sum(1) / seq_len.to(y.dtype).unsqueeze(-1)
+        return torch.softmax(self.head(torch.cat([uid_e, item_eb, pooled], -1)), -1) + 1e-8
+
+
+def bst_train_step(model, batch, dense_opt, ev_opt, global_step=None, world=1, group=None,
+                   staged=False):
+    """One BST step: DIN's loss and update (din_train_step) on the BST model,
+    world > 1 included."""
+    return din_train_step(model, batch, dense_opt, ev_opt, global_step, world, group, staged)
 
 
 def allreduce_dense_grads(params, group=None, staged=False):

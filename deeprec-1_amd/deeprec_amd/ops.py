@@ -1204,6 +1204,126 @@ def gru_sequence(xp, wh_g, wh_c, seq_len, att=None):
 
 
 # ---------------------------------------------------------------------------
+# Multi-head self-attention over a padded history (BST's attention block: the
+# reference multihead_attention, key masking then query masking; DESIGN
+# section 26)
+# ---------------------------------------------------------------------------
+MHA_HEAD_DIMS = (8, 16, 32)
+MHA_MAX_T = 128
+# DR_MHA=torch: the torch composition of the same contract on the GPU too (A/B)
+_MHA_NATIVE = os.environ.get("DR_MHA", "native") != "torch"
+
+
+def mha_native_ok(q, heads):
+    """The kernels take this input: fp32 [B >= 1, 1 <= T <= 128, heads *
+    head_dim] on a GPU with head_dim 8, 16 or 32."""
+    if q.dim() != 3 or heads < 1 or q.shape[2] % heads:
+        return False
+    return (q.is_cuda and q.dtype == torch.float32 and q.shape[0] >= 1
+            and 1 <= q.shape[1] <= MHA_MAX_T and q.shape[2] // heads in MHA_HEAD_DIMS)
+
+
+def _mha_qkv(q, k, v):
+    """q, k, v as the kernels read them: (q, k, v, ld) unchanged when they are
+    fp32 row views with one row stride (the column blocks of a packed
+    projection), contiguous copies otherwise."""
+    B, T, E = q.shape
+    ld = q.stride(1)
+    for t in (q, k, v):
+        if not (t.dtype == torch.float32 and t.shape == q.shape and t.stride(2) == 1
+                and t.stride(1) == ld and t.stride(0) == T * ld and ld % 4 == 0 and ld >= E
+                and t.data_ptr() % 16 == 0):
+            return _c(q, torch.float32), _c(k, torch.float32), _c(v, torch.float32), E
+    return q, k, v, ld
+
+
+def mha_seq_forward(q, k, v, seq_len, heads, scale=None):
+    """dr_mha_seq_forward: q, k, v [B, T, heads * head_dim] (row views with a
+    common stride pass without a copy), seq_len [B] -> (out [B, T, E], saved
+    [B, heads, T] = the rows' logsumexp); zeros at t >= seq_len[b]."""
+    dev = _dev(q)
+    B, T, E = q.shape
+    hd = E // heads
+    scale = float(hd) ** -0.5 if scale is None else float(scale)
+    q, k, v, ld = _mha_qkv(q, k, v)
+    sl = _c(seq_len, torch.int32)
+    out = torch.empty((B, T, E), dtype=torch.float32, device=dev)
+    saved = torch.empty((B, heads, T), dtype=torch.float32, device=dev)
+    check(lib().dr_mha_seq_forward(ptr(q), ptr(k), ptr(v), ld, ptr(sl), B, T, heads, hd, scale,
+                                   ptr(out), ptr(saved), stream_handle(dev)))
+    _post(dev)
+    return out, saved
+
+
+def mha_seq_backward(q, k, v, seq_len, heads, out, saved, grad_out, scale=None):
+    """dr_mha_seq_backward -> (grad_q, grad_k, grad_v), the three column blocks
+    of one packed [B, T, 3E] buffer; zeros at t >= seq_len[b]."""
+    dev = _dev(q)
+    B, T, E = q.shape
+    hd = E // heads
+    scale = float(hd) ** -0.5 if scale is None else float(scale)
+    q, k, v, ld = _mha_qkv(q, k, v)
+    sl = _c(seq_len, torch.int32)
+    g = torch.empty((B, T, 3 * E), dtype=torch.float32, device=dev)
+    gq, gk, gv = g[..., :E], g[..., E:2 * E], g[..., 2 * E:]
+    check(lib().dr_mha_seq_backward(ptr(q), ptr(k), ptr(v), ld, ptr(sl),
+                                    ptr(_c(out, torch.float32)), ptr(_c(saved, torch.float32)),
+                                    ptr(_c(grad_out, torch.float32)), B, T, heads, hd, scale,
+                                    ptr(gq), ptr(gk), ptr(gv), 3 * E, stream_handle(dev)))
+    _post(dev)
+    return gq, gk, gv
+
+
+class _MultiheadAttentionFn(torch.autograd.Function):
+    """One launch each way (dr_mha_seq_forward / _backward)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, seq_len, heads):
+        out, saved = mha_seq_forward(q, k, v, seq_len, heads)
+        ctx.save_for_backward(q, k, v, seq_len, out, saved)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        q, k, v, seq_len, out, saved = ctx.saved_tensors
+        gq, gk, gv = mha_seq_backward(q, k, v, seq_len, ctx.heads, out, saved, g_out)
+        return gq, gk, gv, None, None
+
+
+def _multihead_attention_torch(q, k, v, seq_len, heads):
+    """The contract of dr_mha_seq_forward as a torch composition (autograd
+    forms the backward), in the reference's order: scale, key masking with
+    -2**32 + 1, softmax, query masking, weighted sum.  CPU tensors, shapes
+    outside the kernels' set, and the DR_MHA=torch arm."""
+    B, T, E = q.shape
+    hd = E // heads
+    split = lambda x: x.reshape(B, T, heads, hd).permute(0, 2, 1, 3)  # noqa: E731
+    lens = seq_len.to(q.device).clamp(0, T)
+    live = torch.arange(T, device=q.device)[None, :] < lens[:, None]                # [B, T]
+    s = (split(q) @ split(k).transpose(2, 3)) * (float(hd) ** -0.5)                # [B, h, T, T]
+    s = torch.where(live[:, None, None, :], s, torch.full_like(s, float(-2 ** 32 + 1)))
+    p = torch.softmax(s, -1) * live[:, None, :, None].to(s.dtype)
+    return (p @ split(v)).permute(0, 2, 1, 3).reshape(B, T, E)
+
+
+def multihead_attention(q, k, v, seq_len, heads):
+    """Multi-head self-attention over a padded history -> out [B, T, E]:
+    softmax(q k^T / sqrt(head_dim)) v per head over the first seq_len[b] keys,
+    exact zeros at the padded queries; gradients for q, k and v (views of one
+    packed buffer on the native path).  q, k, v [B, T, E = heads * head_dim]
+    may be the column blocks of one packed projection.  fp32 GPU tensors with
+    head_dim 8 / 16 / 32 and T <= 128 run one HIP kernel each way; anything
+    else (and DR_MHA=torch) the torch composition."""
+    if q.dim() != 3 or heads < 1 or q.shape[2] % heads or k.shape != q.shape or v.shape != q.shape:
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT,
+                                "multihead_attention: q, k, v must be [B, T, heads * head_dim]")
+    if _MHA_NATIVE and mha_native_ok(q, heads):
+        return _MultiheadAttentionFn.apply(q, k, v, seq_len, heads)
+    return _multihead_attention_torch(q, k, v, seq_len, heads)
+
+
+# ---------------------------------------------------------------------------
 # Row-sharded exchange helpers
 # ---------------------------------------------------------------------------
 def partition_by_owner(keys, world, n_dev=None):

@@ -1740,6 +1740,38 @@ int dr_gru_seq_backward(const float* wh_g, const float* wh_c, const int32_t* seq
                         void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Multi-head self-attention over a padded history (BST's attention block:   */
+/* the reference multihead_attention with key masking, then query masking),  */
+/* fp32, forward and backward, one launch each (csrc/mha.hip).    */
+/* q, k, v [B, T, heads * head_dim] views with the common row stride ld      */
+/* (floats, >= heads * head_dim: the column blocks of a packed [B, T, 3E]    */
+/* projection pass as they are); head h is columns [h * head_dim, (h + 1) *  */
+/* head_dim).  With L = clamp(seq_len[b], 0, T), for t < L:                  */
+/*   s[j] = scale * dot(q[b,t,h], k[b,j,h]) (j < L);  p = softmax_j(s)       */
+/*   out[b,t,h] = sum_j p[j] v[b,j,h];  saved[b,h,t] = logsumexp_j(s)        */
+/* and out [B, T, E] (contiguous) and saved [B, heads, T]                    */
+/* (dr_mha_seq_saved_size bytes) are exactly 0 at t >= L.  head_dim 8, 16 or */
+/* 32, heads >= 1, 1 <= T <= 128, B >= 0 (B == 0: nothing is launched), ld   */
+/* a multiple of 4, no null pointer, q / k / v / out / grad_* 16-byte        */
+/* aligned; anything else is DR_INVALID_ARGUMENT.  No allocation, host read, */
+/* synchronisation or atomics.  A (sample, head)'s results depend only on    */
+/* its own first L rows: not on B, the samples around it or T.               */
+/* ------------------------------------------------------------------------ */
+size_t dr_mha_seq_saved_size(int64_t batch, int64_t seq_len, int64_t heads);
+int dr_mha_seq_forward(const float* q, const float* k, const float* v, int64_t ld,
+                       const int32_t* seq_len, int64_t batch, int64_t max_len, int64_t heads,
+                       int64_t head_dim, float scale, float* out, float* saved, void* stream);
+/* Backward: p is recomputed from saved; out and grad_out are [B, T, E]      */
+/* contiguous.  grad_q / grad_k / grad_v are written with their own row      */
+/* stride ld_grad (they may be the column blocks of one packed buffer) and   */
+/* are exactly 0 at t >= L.                                                  */
+int dr_mha_seq_backward(const float* q, const float* k, const float* v, int64_t ld,
+                        const int32_t* seq_len, const float* out, const float* saved,
+                        const float* grad_out, int64_t batch, int64_t max_len, int64_t heads,
+                        int64_t head_dim, float scale, float* grad_q, float* grad_k,
+                        float* grad_v, int64_t ld_grad, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* String -> id, the step before the lookup.  Strings are one byte buffer    */
 /* plus int64 offsets[n+1] (string i = bytes[offsets[i] .. offsets[i+1])).   */
 /* ------------------------------------------------------------------------ */

@@ -5,11 +5,12 @@ BCE loss, backward, dense SGD, KV SGD / Adagrad on every EV; or DIN
 (modelzoo/DIN, BASELINE configs[3]: uid / item / category EVs of dim 18,
 history lengths U[1, maxlen], Adam as in the reference) or DIEN (the same
 shape plus one negative sample per history position; DR_GRU=torch runs its
-GRUs as torch compositions, the A/B arm).  Prints one JSON
+GRUs as torch compositions, the A/B arm) or BST (DIN's batch; DR_MHA=torch
+runs its attention as a torch composition).  Prints one JSON
 line with samples/s and the per-phase split.  A measurement aid for
 SURVEY 8f #4; bench.py's headline metric is the forward lookup.
 
-  python tools/model_step.py [--model dlrm|deepfm|din|dien|dcn|wdl] [--rows 12500000] [--dim 128]
+  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|dcn|wdl] [--rows 12500000] [--dim 128]
 """
 import argparse
 import json
@@ -25,7 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "deeprec-1_amd"))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="dlrm", choices=["dlrm", "deepfm", "din", "dien", "dcn", "wdl"])
+    ap.add_argument("--model", default="dlrm", choices=["dlrm", "deepfm", "din", "dien", "bst", "dcn", "wdl"])
     ap.add_argument("--maxlen", type=int, default=100, help="DIN history length bound")
     ap.add_argument("--tables", type=int, default=26)
     ap.add_argument("--rows", type=int, default=12_500_000)
@@ -40,7 +41,7 @@ def main():
     from deeprec_amd import modelzoo as mz
     dr.load()
     dev = torch.device("cuda", 0)
-    if args.model in ("din", "dien"):
+    if args.model in ("din", "dien", "bst"):
         args.batch = args.batch or 4096
         return din(args, dr, mz, dev)
     if args.model == "wdl":
@@ -155,8 +156,9 @@ def din(args, dr, mz, dev):
         ev = dr.EmbeddingVariable("din%d" % i, D, 0.0, capacity=r + (1 << 16), device=dev)
         ev.insert_synthetic(0, r, seed=700 + i)
         evs.append(ev)
-    model = (mz.DIEN if dien else mz.DIN)(*evs).to(dev)
-    step = mz.dien_train_step if dien else mz.din_train_step
+    bst = args.model == "bst"
+    model = (mz.DIEN if dien else mz.BST if bst else mz.DIN)(*evs).to(dev)
+    step = mz.dien_train_step if dien else mz.bst_train_step if bst else mz.din_train_step
     dopt = torch.optim.Adam(model.parameters(), lr=0.001)
     eopt = dr.AdamOptimizer(0.001)
     g = torch.Generator(device=dev)
@@ -194,6 +196,8 @@ def din(args, dr, mz, dev):
            "dim": D, "vocab": R, "opt": "adam", "loss": float(loss)}
     if dien:
         res["gru"] = os.environ.get("DR_GRU", "native")
+    if bst:
+        res["mha"] = os.environ.get("DR_MHA", "native")
     print(json.dumps(res), flush=True)
 
 
