@@ -449,6 +449,10 @@ SIGNATURES = {
     "dr_mha_seq_forward": (_I32, [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _F32, _P, _P, _P]),
     "dr_mha_seq_backward": (_I32, [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F32,
                                    _P, _P, _P, _I64, _P]),
+    "dr_gate_mix_saved_size": (_SZ, [_I64, _I64, _I64]),
+    "dr_gate_mix_forward": (_I32, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
+    "dr_gate_mix_backward": (_I32, [_P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P,
+                                    _P]),
     "dr_fingerprint64": (_I32, [_P, _P, _I64, _P, _P]),
     "dr_string_to_hash_bucket_fast": (_I32, [_P, _P, _I64, _I64, _P, _P]),
     "dr_crc32c_extend": (C.c_uint32, [C.c_uint32, _P, _SZ]),

@@ -22,6 +22,8 @@ north_star asks.
   gated GRU, csrc/gru.hip) and the auxiliary loss (DIEN class below).
 * BST: the Behavior Sequence Transformer on DIN's inputs; its multi-head
   self-attention is csrc/mha.hip (MultiHeadAttention and BST classes below).
+* MMoE, PLE: the multi-task models; their gate softmax and expert mixing is
+  csrc/gate_mix.hip (ops.gate_mix; MMoE and PLE classes below).
 * WDL: modelzoo/WDL/train.py:182-335 (WDL class below).
 * DCN-v2: stacked cross network on the MFMA kernel (DCNv2 class below).
 
@@ -1452,6 +1454,156 @@ def bst_train_step(model, batch, dense_opt, ev_opt, global_step=None, world=1, g
     """One BST step: DIN's loss and update (din_train_step) on the BST model,
     world > 1 included."""
     return din_train_step(model, batch, dense_opt, ev_opt, global_step, world, group, staged)
+
+
+class _ExpertStack(torch.nn.Module):
+    """n experts of equal layer sizes as one stack, relu after every layer ->
+    [B, n, sizes[-1]].  A shared input [B, n_in] goes through one Linear of
+    width n * sizes[0]; per-expert inputs [n, B, n_in] (grouped=True) through
+    a grouped product.  Later layers are grouped products (baddbmm over the
+    [n, B, .] view)."""
+
+    def __init__(self, n_in, n, sizes, grouped=False):
+        super().__init__()
+        self.n, sizes = n, list(sizes)
+        self.first = None if grouped else torch.nn.Linear(n_in, n * sizes[0])
+        dims = ([n_in] if grouped else []) + sizes
+        self.weights, self.biases = torch.nn.ParameterList(), torch.nn.ParameterList()
+        for i, o in zip(dims[:-1], dims[1:]):
+            bound = float(i) ** -0.5                        # torch.nn.Linear's default range
+            self.weights.append(torch.nn.Parameter(torch.empty(n, i, o).uniform_(-bound, bound)))
+            self.biases.append(torch.nn.Parameter(torch.empty(n, 1, o).uniform_(-bound, bound)))
+
+    def forward(self, x):
+        if self.first is not None:
+            x = torch.relu(self.first(x)).view(x.shape[0], self.n, -1).transpose(0, 1)
+        for w, b in zip(self.weights, self.biases):
+            x = torch.relu(torch.baddbmm(b, x, w))
+        return x.transpose(0, 1)
+
+
+class _TaskTowers(torch.nn.Module):
+    """One tower and one sigmoid per task over the column blocks of the
+    mixtures [B, >= tasks, H] -> [B, tasks]."""
+
+    def __init__(self, n_in, tasks, tower_sizes, bf16=False):
+        super().__init__()
+        self.bf16 = _MaybeBF16(bf16)
+        self.towers = torch.nn.ModuleList(
+            _mlp([n_in] + list(tower_sizes) + [1], last_act=False) for _ in range(tasks))
+
+    def forward(self, mix):
+        return torch.sigmoid(torch.cat([self.bf16(t, mix[:, k])
+                                        for k, t in enumerate(self.towers)], 1))
+
+
+class _MultiTaskInput(torch.nn.Module):
+    """[one-hot lookups | dense features] -> [B, T * dim + dense_dim], as
+    DeepFM's dnn input; dense tables on CPU tensors, as for DIEN."""
+
+    def __init__(self, evs, dense_dim):
+        super().__init__()
+        self.evs = list(evs)
+        self.n_in = sum(ev.dim for ev in self.evs) + dense_dim
+        self.lookup = _OneHotLookup(self.evs)
+
+    def _input(self, dense, ids, anchor):
+        emb = (self.lookup(ids) if ids.is_cuda
+               else _HostTableLookupFn.apply(anchor, self.evs, ids))
+        return torch.cat([emb, dense], 1)
+
+
+class MMoE(_MultiTaskInput):
+    """Multi-gate Mixture-of-Experts (Ma et al., KDD 2018) over the DeepFM
+    input x = [lookups | dense]:
+      h_e = expert_e(x), e < experts (one stack: the first layer is one Linear
+            of width experts * expert_sizes[0], later layers grouped products)
+      g_k = softmax(x W_g[:, k]) over the experts, all gates from one Linear
+      y_k = sigmoid(tower_k(sum_e g_k[e] h_e))           -> [B, tasks]
+    The mixtures are one ops.gate_mix call.  bf16=True runs the towers as the
+    reference's --bf16 does; the experts and the mixing stay fp32."""
+
+    def __init__(self, evs, dense_dim, experts=8, expert_sizes=(256, 128), tasks=2,
+                 tower_sizes=(64,), bf16=False):
+        super().__init__(evs, dense_dim)
+        self.tasks, self.num_experts = tasks, experts
+        self.experts = _ExpertStack(self.n_in, experts, expert_sizes)
+        self.gates = torch.nn.Linear(self.n_in, tasks * experts)
+        self.towers = _TaskTowers(expert_sizes[-1], tasks, tower_sizes, bf16)
+
+    def forward(self, dense, ids):
+        x = self._input(dense, ids, self.gates.bias)
+        z = self.gates(x).view(-1, self.tasks, self.num_experts)
+        return self.towers(ops.gate_mix(z, self.experts(x)))
+
+
+class PLE(_MultiTaskInput):
+    """Progressive Layered Extraction (Tang et al., RecSys 2020) over the
+    DeepFM input x.  Every level l has E = tasks * specific + shared experts
+    in one stack: experts [k * specific, (k + 1) * specific) belong to task k,
+    the last `shared` ones to all.  With u_k^0 = u_s^0 = x:
+      h_e^l = expert_e^l(u_k^{l-1}) for task k's experts, expert_e^l(u_s^{l-1})
+              for the shared ones
+      u_k^l = sum_{e in S_k} softmax_{S_k}(u_k^{l-1} W_k^l)[e] h_e^l, S_k = task
+              k's experts and the shared ones
+      u_s^l = sum_e softmax(u_s^{l-1} W_s^l)[e] h_e^l over all E experts, at
+              every level but the last
+      y_k   = sigmoid(tower_k(u_k^{levels}))             -> [B, tasks]
+    A level is one ops.gate_mix call with the [K, E] select mask, K = tasks +
+    1 rows (the last with every bit set) below the last level and K = tasks
+    rows at it."""
+
+    def __init__(self, evs, dense_dim, specific=2, shared=2, levels=2, expert_sizes=(128,),
+                 tasks=2, tower_sizes=(64,)):
+        super().__init__(evs, dense_dim)
+        self.tasks, self.levels = tasks, levels
+        E, H = tasks * specific + shared, expert_sizes[-1]
+        self.num_experts = E
+        own = torch.zeros(tasks + 1, E, dtype=torch.bool)
+        for k in range(tasks):
+            own[k, k * specific:(k + 1) * specific] = True
+        own[:, tasks * specific:] = True
+        self.reads = [k for k in range(tasks) for _ in range(specific)] + [tasks] * shared
+        own[tasks] = True
+        self.select = [own if l + 1 < levels else own[:tasks] for l in range(levels)]
+        self.experts = torch.nn.ModuleList(
+            _ExpertStack(self.n_in if l == 0 else H, E, expert_sizes, grouped=l > 0)
+            for l in range(levels))
+        self.gate0 = torch.nn.Linear(self.n_in, self.select[0].shape[0] * E)
+        # the gates above the first level read their own mixture: a grouped Linear
+        self.gate_w = torch.nn.ParameterList(
+            torch.nn.Parameter(torch.empty(self.select[l].shape[0], H, E).uniform_(-1, 1) * H ** -0.5)
+            for l in range(1, levels))
+        self.gate_b = torch.nn.ParameterList(
+            torch.nn.Parameter(torch.zeros(self.select[l].shape[0], 1, E)) for l in range(1, levels))
+        self.towers = _TaskTowers(H, tasks, tower_sizes)
+
+    def forward(self, dense, ids):
+        x = self._input(dense, ids, self.gate0.bias)
+        K = self.select[0].shape[0]
+        mix = ops.gate_mix(self.gate0(x).view(-1, K, self.num_experts), self.experts[0](x),
+                           self.select[0])
+        for l in range(1, self.levels):
+            u = mix.transpose(0, 1)                                  # [K, B, H]
+            K = self.select[l].shape[0]
+            z = torch.baddbmm(self.gate_b[l - 1], u[:K], self.gate_w[l - 1]).transpose(0, 1)
+            mix = ops.gate_mix(z, self.experts[l](u[self.reads]), self.select[l])
+        return self.towers(mix)
+
+
+def multitask_train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step=None):
+    """One step of a multi-task model (MMoE, PLE): labels [B, tasks]; the loss
+    is the sum over the tasks of the mean BCE (train_step's eps clip); then
+    the dense optimizer and the KV optimizer on model.evs."""
+    pred = model(dense, ids)
+    eps = 1e-7
+    p = pred.clamp(eps, 1 - eps)
+    loss = -(labels * torch.log(p) + (1 - labels) * torch.log(1 - p)).mean(0).sum()
+    dense_opt.zero_grad(set_to_none=True)
+    loss.backward()
+    dense_opt.step()
+    ev_opt.apply_gradients(list(model.evs), global_step=global_step)
+    return loss
 
 
 def allreduce_dense_grads(params, group=None, staged=False):

@@ -1324,6 +1324,137 @@ def multihead_attention(q, k, v, seq_len, heads):
 
 
 # ---------------------------------------------------------------------------
+# Gate softmax and expert mixing (the block of the multi-task models MMoE and
+# PLE: per task a softmax gate over the experts it may see, and the gate-
+# weighted mixture of the expert outputs)
+# ---------------------------------------------------------------------------
+GATE_MIX_MAX = (8, 16, 512)             # tasks, experts, expert width
+# DR_GATE_MIX=torch: the torch composition of the same contract on the GPU too (A/B)
+_GATE_MIX_NATIVE = os.environ.get("DR_GATE_MIX", "native") != "torch"
+
+
+def gate_mix_native_ok(logits, experts):
+    """The kernels take this input: fp32 [B >= 1, K <= 8, E <= 16] and [B, E,
+    H] on a GPU with H a multiple of 4 in [4, 512]."""
+    if logits.dim() != 3 or experts.dim() != 3:
+        return False
+    (B, K, E), H = logits.shape, experts.shape[2]
+    return (logits.is_cuda and logits.dtype == torch.float32 and experts.dtype == torch.float32
+            and B >= 1 and 1 <= K <= GATE_MIX_MAX[0] and 1 <= E <= GATE_MIX_MAX[1]
+            and H % 4 == 0 and 4 <= H <= GATE_MIX_MAX[2])
+
+
+def _gate_mix_rows(x):
+    """[B, N, W] as the kernels read it, rows of N * W floats: (x, row stride)
+    unchanged for an fp32 view with one row stride (a column block of a wider
+    buffer), a copy with the row stride rounded up to 4 floats otherwise (K * E
+    need not be a multiple of 4)."""
+    B, N, W = x.shape
+    ld = -(-N * W // 4) * 4
+    if (x.dtype == torch.float32 and x.stride(2) == 1 and (N == 1 or x.stride(1) == W)
+            and (x.stride(0) >= ld and x.stride(0) % 4 == 0 if B > 1 else ld == N * W)
+            and x.data_ptr() % 16 == 0):
+        return x, (x.stride(0) if B > 1 else ld)
+    rows = torch.empty((B, ld), dtype=torch.float32, device=x.device)
+    rows[:, :N * W] = x.reshape(B, N * W)
+    return rows, ld
+
+
+def _gate_mix_select(select, K, E):
+    """select (None, or a [K, E] bool tensor or nested list) as the K host
+    words of the C entries (bit e of word k: task k sees expert e) and as the
+    bool tensor."""
+    if select is None or isinstance(select, C.Array):      # (already the words)
+        return select, None
+    sel = torch.as_tensor(select, dtype=torch.bool).cpu()
+    if sel.shape != (K, E):
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT, "gate_mix: select must be [tasks, experts]")
+    words = (sel.long() << torch.arange(E)).sum(1).tolist()
+    return (C.c_uint32 * K)(*words), sel
+
+
+def gate_mix_forward(logits, experts, select=None):
+    """dr_gate_mix_forward: logits [B, K, E], experts [B, E, H] (views with a
+    row stride pass without a copy) -> (out [B, K, H], gates [B, K, E])."""
+    dev = _dev(experts)
+    (B, K, E), H = logits.shape, experts.shape[2]
+    z, ld_z = _gate_mix_rows(logits)
+    h, ld_h = _gate_mix_rows(experts)
+    words, _ = _gate_mix_select(select, K, E)
+    out = torch.empty((B, K, H), dtype=torch.float32, device=dev)
+    gates = torch.empty(lib().dr_gate_mix_saved_size(B, K, E) // 4, dtype=torch.float32,
+                        device=dev).view(B, K, E)
+    check(lib().dr_gate_mix_forward(ptr(z), ld_z, ptr(h), ld_h, words, B, K, E, H, ptr(out),
+                                    ptr(gates), stream_handle(dev)))
+    _post(dev)
+    return out, gates
+
+
+def gate_mix_backward(experts, gates, grad_out, select=None):
+    """dr_gate_mix_backward -> (grad_logits [B, K, E], grad_experts [B, E, H])."""
+    dev = _dev(experts)
+    (B, K, E), H = gates.shape, experts.shape[2]
+    h, ld_h = _gate_mix_rows(experts)
+    go, ld_go = _gate_mix_rows(grad_out)
+    words, _ = _gate_mix_select(select, K, E)
+    gz = torch.empty((B, K, E), dtype=torch.float32, device=dev)
+    gh = torch.empty((B, E, H), dtype=torch.float32, device=dev)
+    check(lib().dr_gate_mix_backward(ptr(h), ld_h, ptr(_c(gates, torch.float32)), ptr(go), ld_go,
+                                     words, B, K, E, H, ptr(gz), ptr(gh), stream_handle(dev)))
+    _post(dev)
+    return gz, gh
+
+
+class _GateMixFn(torch.autograd.Function):
+    """One launch each way (dr_gate_mix_forward / _backward); the gates are
+    the only saved extra."""
+
+    @staticmethod
+    def forward(ctx, logits, experts, select):
+        ctx.select = _gate_mix_select(select, logits.shape[1], logits.shape[2])[0]
+        out, gates = gate_mix_forward(logits, experts, ctx.select)
+        ctx.save_for_backward(experts, gates)
+        ctx.mark_non_differentiable(gates)
+        return out, gates
+
+    @staticmethod
+    def backward(ctx, g_out, _g_gates):
+        experts, gates = ctx.saved_tensors
+        gz, gh = gate_mix_backward(experts, gates, g_out, ctx.select)
+        return gz, gh, None
+
+
+def _gate_mix_torch(logits, experts, select=None):
+    """The contract of dr_gate_mix_forward as a torch composition (autograd
+    forms the backward) -> (out, gates): CPU tensors, shapes outside the
+    kernels' set, and the DR_GATE_MIX=torch arm."""
+    _, sel = _gate_mix_select(select, logits.shape[1], logits.shape[2])
+    z = logits
+    if sel is not None:
+        z = z.masked_fill(~sel.to(z.device), float("-inf"))
+    gates = torch.softmax(z, -1)
+    return torch.bmm(gates, experts), gates
+
+
+def gate_mix(logits, experts, select=None):
+    """The multi-gate mixture of experts -> out [B, K, H]: out[b, k] = sum_e
+    softmax_e(logits[b, k])[e] * experts[b, e], the softmax over the experts
+    task k may see (select [K, E] bool tensor or nested list; None = all) and
+    exactly 0 on the others; gradients for logits and experts.  Both inputs
+    may be views with a row stride (the output of one Linear, a column block).
+    fp32 GPU tensors with K <= 8, E <= 16 and H a multiple of 4 up to 512 run
+    one HIP kernel each way; anything else (and DR_GATE_MIX=torch) the torch
+    composition."""
+    if (logits.dim() != 3 or experts.dim() != 3 or logits.shape[0] != experts.shape[0]
+            or logits.shape[2] != experts.shape[1]):
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT,
+                                "gate_mix: logits must be [B, K, E] and experts [B, E, H]")
+    if _GATE_MIX_NATIVE and gate_mix_native_ok(logits, experts):
+        return _GateMixFn.apply(logits, experts, select)[0]
+    return _gate_mix_torch(logits, experts, select)[0]
+
+
+# ---------------------------------------------------------------------------
 # Row-sharded exchange helpers
 # ---------------------------------------------------------------------------
 def partition_by_owner(keys, world, n_dev=None):

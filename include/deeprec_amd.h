@@ -1772,6 +1772,46 @@ int dr_mha_seq_backward(const float* q, const float* k, const float* v, int64_t 
                         float* grad_v, int64_t ld_grad, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Gate softmax and expert mixing, the block that defines the multi-task     */
+/* models MMoE and PLE, fp32, forward and backward, one launch each          */
+/* (csrc/gate_mix.hip).  z [B, >= K * E] (row stride ld_z) holds   */
+/* task k's logits at columns [k * E, (k + 1) * E): one Linear for all gates. */
+/* h [B, >= E * H] (row stride ld_h) holds expert e at columns [e * H,       */
+/* (e + 1) * H); it may be a column block of something wider.  select_bits   */
+/* is a HOST pointer to K words, bit e of word k set when task k may see     */
+/* expert e (the set S_k), or NULL for every expert; it is read at call time */
+/* and passed to the kernel by value, so a captured launch keeps it.         */
+/*   gates[b,k,e] = softmax over e in S_k of z[b,k,e];  exactly 0 outside S_k */
+/*   out[b,k,:]   = sum_e gates[b,k,e] h[b,e,:]                              */
+/* out is [B, K * H] contiguous (task k's tower input is a column block) and */
+/* gates [B, K, E] contiguous (dr_gate_mix_saved_size bytes), saved for the  */
+/* backward.  1 <= K <= 8, 1 <= E <= 16, H a multiple of 4 in [4, 512],      */
+/* B >= 0 (B == 0: nothing is launched), strides multiples of 4 floats, no   */
+/* null data pointer, data pointers 16-byte aligned, every selection word    */
+/* non-zero and below 1 << E; anything else is DR_INVALID_ARGUMENT.  No      */
+/* allocation, host read, synchronisation or atomics.  A sample's results    */
+/* are bitwise independent of B, of its position and of its neighbours: all  */
+/* sums run over e, k or the columns in ascending order in one lane, except  */
+/* dg's sum over the lanes of a sample, a butterfly fixed by H.              */
+/* ------------------------------------------------------------------------ */
+size_t dr_gate_mix_saved_size(int64_t batch, int64_t tasks, int64_t experts);
+int dr_gate_mix_forward(const float* z, int64_t ld_z, const float* h, int64_t ld_h,
+                        const uint32_t* select_bits /* host, nullable */, int64_t batch,
+                        int64_t tasks, int64_t experts, int64_t width, float* out, float* gates,
+                        void* stream);
+/* Backward from go [B, >= K * H] (row stride ld_go) and the saved gates:    */
+/*   grad_h[b,e,:] = sum_k gates[b,k,e] go[b,k,:]                            */
+/*   dg[b,k,e]     = dot(go[b,k,:], h[b,e,:])                                */
+/*   grad_z[b,k,e] = gates[b,k,e] (dg[b,k,e] - sum_e' gates[b,k,e'] dg[b,k,e']) */
+/* grad_z [B, K * E] and grad_h [B, E * H] are contiguous and written in     */
+/* full (no accumulate); grad_z is exactly 0 outside S_k and for a row with  */
+/* one selected expert.                                                      */
+int dr_gate_mix_backward(const float* h, int64_t ld_h, const float* gates, const float* go,
+                         int64_t ld_go, const uint32_t* select_bits /* host, nullable */,
+                         int64_t batch, int64_t tasks, int64_t experts, int64_t width,
+                         float* grad_z, float* grad_h, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* String -> id, the step before the lookup.  Strings are one byte buffer    */
 /* plus int64 offsets[n+1] (string i = bytes[offsets[i] .. offsets[i+1])).   */
 /* ------------------------------------------------------------------------ */

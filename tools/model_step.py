@@ -6,11 +6,13 @@ BCE loss, backward, dense SGD, KV SGD / Adagrad on every EV; or DIN
 history lengths U[1, maxlen], Adam as in the reference) or DIEN (the same
 shape plus one negative sample per history position; DR_GRU=torch runs its
 GRUs as torch compositions, the A/B arm) or BST (DIN's batch; DR_MHA=torch
-runs its attention as a torch composition).  Prints one JSON
+runs its attention as a torch composition) or MMoE / PLE (DeepFM's synthetic
+batch with two random label columns; DR_GATE_MIX=torch runs the gate softmax
+and expert mixing as a torch composition).  Prints one JSON
 line with samples/s and the per-phase split.  A measurement aid for
 SURVEY 8f #4; bench.py's headline metric is the forward lookup.
 
-  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|dcn|wdl] [--rows 12500000] [--dim 128]
+  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|mmoe|ple|dcn|wdl] [--rows 12500000] [--dim 128]
 """
 import argparse
 import json
@@ -26,7 +28,8 @@ sys.path.insert(0, os.path.join(ROOT, "deeprec-1_amd"))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="dlrm", choices=["dlrm", "deepfm", "din", "dien", "bst", "dcn", "wdl"])
+    ap.add_argument("--model", default="dlrm",
+                    choices=["dlrm", "deepfm", "din", "dien", "bst", "mmoe", "ple", "dcn", "wdl"])
     ap.add_argument("--maxlen", type=int, default=100, help="DIN history length bound")
     ap.add_argument("--tables", type=int, default=26)
     ap.add_argument("--rows", type=int, default=12_500_000)
@@ -57,6 +60,9 @@ def main():
         evs.append(ev)
     if args.model == "dlrm":
         model = mz.DLRM(evs, 13, (512, 256), (512, 256), bf16=args.bf16).to(dev)
+    elif args.model in ("mmoe", "ple"):
+        model = mz.MMoE(evs, 13, bf16=args.bf16) if args.model == "mmoe" else mz.PLE(evs, 13)
+        model = model.to(dev)
     elif args.model == "dcn":     # BASELINE configs[4]: bf16 CrossNet on MFMA, 3 layers
         model = mz.DCNv2(evs, 13, layers=3, deep=(1024, 512), bf16=args.bf16).to(dev)
     else:
@@ -76,20 +82,28 @@ def main():
     batches = [(torch.randn(B, 13, generator=g, device=dev),
                 torch.randint(0, R, (T, B), generator=g, device=dev),
                 (torch.rand(B, generator=g, device=dev) > 0.5).float()) for _ in range(4)]
+    step = mz.train_step
+    if args.model in ("mmoe", "ple"):                       # two objectives: [B, 2] labels
+        batches = [(d, i, torch.stack([l, (torch.rand(B, generator=g, device=dev) > 0.5).float()],
+                                      1)) for d, i, l in batches]
+        step = mz.multitask_train_step
     for i in range(args.warmup):
-        mz.train_step(model, *batches[i % 4][:2], batches[i % 4][2], dopt, eopt, i)
+        step(model, *batches[i % 4][:2], batches[i % 4][2], dopt, eopt, i)
     torch.cuda.synchronize()
     print("[model_step] warmup ok", file=sys.stderr, flush=True)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = mz.train_step(model, *batches[i % 4][:2], batches[i % 4][2], dopt, eopt, i)
+        loss = step(model, *batches[i % 4][:2], batches[i % 4][2], dopt, eopt, i)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     dr.status_check(dev)
-    print(json.dumps({"model": args.model, "samples_per_s": round(B * args.steps / el, 1),
-                      "lookups_per_s": round(T * B * args.steps / el, 1),
-                      "ms_per_step": round(el / args.steps * 1e3, 3), "batch": B, "tables": T,
-                      "rows": R, "dim": D, "opt": args.opt, "bf16_mlp": args.bf16, "loss": float(loss)}), flush=True)
+    res = {"model": args.model, "samples_per_s": round(B * args.steps / el, 1),
+           "lookups_per_s": round(T * B * args.steps / el, 1),
+           "ms_per_step": round(el / args.steps * 1e3, 3), "batch": B, "tables": T,
+           "rows": R, "dim": D, "opt": args.opt, "bf16_mlp": args.bf16, "loss": float(loss)}
+    if args.model in ("mmoe", "ple"):
+        res["gate_mix"] = os.environ.get("DR_GATE_MIX", "native")
+    print(json.dumps(res), flush=True)
 
 
 # modelzoo/WDL/train.py:23-81: per-column hash buckets and embedding dims
