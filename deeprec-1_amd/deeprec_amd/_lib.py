@@ -453,6 +453,12 @@ SIGNATURES = {
     "dr_gate_mix_forward": (_I32, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "dr_gate_mix_backward": (_I32, [_P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P,
                                     _P]),
+    "dr_layer_norm_saved_size": (_SZ, [_I64]),
+    "dr_layer_norm_workspace_size": (_SZ, [_I64, _I64]),
+    "dr_layer_norm_forward": (_I32, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _F32,
+                                     _I32, _P, _P, _P]),
+    "dr_layer_norm_backward": (_I32, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _I64,
+                                      _I64, _I64, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "dr_fingerprint64": (_I32, [_P, _P, _I64, _P, _P]),
     "dr_string_to_hash_bucket_fast": (_I32, [_P, _P, _I64, _I64, _P, _P]),
     "dr_crc32c_extend": (C.c_uint32, [C.c_uint32, _P, _SZ]),

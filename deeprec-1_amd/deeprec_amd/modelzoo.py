@@ -24,6 +24,8 @@ north_star asks.
   self-attention is csrc/mha.hip (MultiHeadAttention and BST classes below).
 * MMoE, PLE: the multi-task models; their gate softmax and expert mixing is
   csrc/gate_mix.hip (ops.gate_mix; MMoE and PLE classes below).
+* MaskNet: serial and parallel MaskBlocks; every LayerNorm with its relu and
+  mask product is csrc/layer_norm.hip (ops.layer_norm; MaskNet class below).
 * WDL: modelzoo/WDL/train.py:182-335 (WDL class below).
 * DCN-v2: stacked cross network on the MFMA kernel (DCNv2 class below).
 
@@ -1604,6 +1606,76 @@ def multitask_train_step(model, dense, ids, labels, dense_opt, ev_opt, global_st
     dense_opt.step()
     ev_opt.apply_gradients(list(model.evs), global_step=global_step)
     return loss
+
+
+class MaskNet(_MultiTaskInput):
+    """MaskNet (Wang et al., 2021; the reference zoo's MaskNet) over the DeepFM
+    input: emb = the one-hot lookups [B, T * dim], x = [emb | dense].  Block i
+    has an instance-guided mask, mask_i = W2_i relu(W1_i x) (aggregation width
+    reduction * the width of x), a bias-free Linear to block_dim and a
+    LayerNorm + relu:
+      serial:   h_1 = LN(emb) * mask_1,  out_i = relu(LN(W_i h_i)),
+                h_{i+1} = out_i * mask_{i+1};  the head reads out_blocks
+      parallel: h_p = LN(emb) * mask_p for every block from one call,
+                out_p = relu(LN(W_p h_p));  the head reads [out_1 | ... ]
+    and y = sigmoid(head(.)) -> [B].  Every LN, with the product that follows
+    it, is one ops.layer_norm call: the serial model fuses mask_{i+1} into
+    block i's call (relu=True, mask=...), the parallel model reads emb once
+    for all its blocks.  bf16=True runs the head as the reference's --bf16
+    does; the blocks stay fp32.  On CPU tensors the variables are dense
+    tables, as for DIEN."""
+
+    def __init__(self, evs, dense_dim, mode="serial", blocks=3, block_dim=512, reduction=2.0,
+                 head_sizes=(256, 128), bf16=False, eps=1e-8):
+        super().__init__(evs, dense_dim)
+        if mode not in ("serial", "parallel") or blocks < 1:
+            raise DeepRecError(INVALID_ARGUMENT, "MaskNet: mode is serial or parallel, blocks >= 1")
+        self.mode, self.blocks, self.block_dim, self.eps = mode, blocks, block_dim, eps
+        self.bf16 = _MaybeBF16(bf16)
+        E, agg = self.n_in - dense_dim, max(1, int(reduction * self.n_in))
+        self.emb_dim = E
+        # the width block i reads (and its mask has): emb, or the block before it
+        reads = [E if mode == "parallel" or i == 0 else block_dim for i in range(blocks)]
+        self.masks = torch.nn.ModuleList(
+            torch.nn.Sequential(torch.nn.Linear(self.n_in, agg), torch.nn.ReLU(),
+                                torch.nn.Linear(agg, w)) for w in reads)
+        self.emb_gain = torch.nn.Parameter(torch.ones(E))
+        self.emb_bias = torch.nn.Parameter(torch.zeros(E))
+        bound = float(E) ** -0.5
+        if mode == "parallel":          # one grouped product for all blocks
+            self.weight = torch.nn.Parameter(torch.empty(blocks, E, block_dim).uniform_(-bound, bound))
+        else:
+            self.linears = torch.nn.ModuleList(
+                torch.nn.Linear(w, block_dim, bias=False) for w in reads)
+        self.gains = torch.nn.Parameter(torch.ones(blocks, block_dim))
+        self.biases = torch.nn.Parameter(torch.zeros(blocks, block_dim))
+        width = block_dim * (blocks if mode == "parallel" else 1)
+        self.head = _mlp([width] + list(head_sizes) + [1], last_act=False)
+
+    def forward(self, dense, ids):
+        emb = (self.lookup(ids) if ids.is_cuda
+               else _HostTableLookupFn.apply(self.emb_bias, self.evs, ids))
+        x = torch.cat([emb, dense], 1)
+        if self.mode == "parallel":
+            mask = torch.stack([m(x) for m in self.masks], 1)                       # [B, P, E]
+            h = ops.layer_norm(emb, self.emb_gain, self.emb_bias, self.eps, mask=mask)
+            hid = torch.bmm(h.transpose(0, 1), self.weight)                         # [P, B, H]
+            out = torch.cat([ops.layer_norm(hid[p], self.gains[p], self.biases[p], self.eps,
+                                            relu=True) for p in range(self.blocks)], 1)
+        else:
+            out = ops.layer_norm(emb, self.emb_gain, self.emb_bias, self.eps,
+                                 mask=self.masks[0](x).unsqueeze(1))[:, 0]
+            for i, lin in enumerate(self.linears):
+                nxt = self.masks[i + 1](x).unsqueeze(1) if i + 1 < self.blocks else None
+                out = ops.layer_norm(lin(out), self.gains[i], self.biases[i], self.eps,
+                                     relu=True, mask=nxt)
+                out = out if nxt is None else out[:, 0]
+        return torch.sigmoid(self.bf16(self.head, out)).squeeze(1)
+
+
+def masknet_train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step=None):
+    """One MaskNet step: train_step's loss and update (labels [B])."""
+    return train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step)
 
 
 def allreduce_dense_grads(params, group=None, staged=False):

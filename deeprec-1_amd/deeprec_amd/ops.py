@@ -1455,6 +1455,132 @@ def gate_mix(logits, experts, select=None):
 
 
 # ---------------------------------------------------------------------------
+# Layer normalisation with a residual add in front and a relu and P
+# elementwise masks behind (BST's normalize, every MaskBlock of MaskNet;
+# DESIGN section 28)
+# ---------------------------------------------------------------------------
+LAYER_NORM_MAX = (1024, 8)              # width, masks
+# DR_LAYER_NORM=torch: the torch composition of the same contract on the GPU too (A/B)
+_LAYER_NORM_NATIVE = os.environ.get("DR_LAYER_NORM", "native") != "torch"
+
+
+def layer_norm_native_ok(x, gain, bias, residual=None, mask=None):
+    """The kernels take this input: fp32 GPU tensors, x [B >= 1, D] with D a
+    multiple of 4 in [4, 1024], and at most 8 masks [B, P, D]."""
+    ts = [t for t in (x, gain, bias, residual, mask) if t is not None]
+    if x.dim() != 2 or not all(t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    B, D = x.shape
+    return (B >= 1 and D % 4 == 0 and 4 <= D <= LAYER_NORM_MAX[0]
+            and (mask is None or 1 <= mask.shape[1] <= LAYER_NORM_MAX[1]))
+
+
+def _layer_norm_rows(x):
+    """[B, D] or [B, P, D] as the kernels read it, (x, row stride) or (NULL,
+    0) for None: _gate_mix_rows' rule, a column block passes without a copy."""
+    if x is None:
+        return None, 0
+    return _gate_mix_rows(x if x.dim() == 3 else x.unsqueeze(1))
+
+
+def layer_norm_forward(x, gain, bias, eps, residual=None, mask=None, relu=False):
+    """dr_layer_norm_forward -> (out [B, D] or [B, P, D], saved [B, 2] = (mean,
+    rstd)); x, residual and mask may be views with a row stride."""
+    dev = _dev(x)
+    B, D = x.shape
+    P = 1 if mask is None else mask.shape[1]
+    xs, ld_x = _layer_norm_rows(x)
+    rs, ld_r = _layer_norm_rows(residual)
+    ms, ld_m = _layer_norm_rows(mask)
+    out = torch.empty((B, D) if mask is None else (B, P, D), dtype=torch.float32, device=dev)
+    saved = torch.empty(lib().dr_layer_norm_saved_size(B) // 4, dtype=torch.float32,
+                        device=dev).view(B, 2)
+    check(lib().dr_layer_norm_forward(ptr(xs), ld_x, ptr(rs), ld_r, ptr(_c(gain, torch.float32)),
+                                      ptr(_c(bias, torch.float32)), ptr(ms), ld_m, B, D, P,
+                                      float(eps), int(bool(relu)), ptr(out), ptr(saved),
+                                      stream_handle(dev)))
+    _post(dev)
+    return out, saved
+
+
+def layer_norm_backward(x, gain, bias, saved, grad_out, residual=None, mask=None, relu=False):
+    """dr_layer_norm_backward -> (grad_x [B, D], grad_mask [B, P, D] or None,
+    grad_gain [D], grad_bias [D]); the gradient of residual is grad_x."""
+    dev = _dev(x)
+    B, D = x.shape
+    P = 1 if mask is None else mask.shape[1]
+    xs, ld_x = _layer_norm_rows(x)
+    rs, ld_r = _layer_norm_rows(residual)
+    ms, ld_m = _layer_norm_rows(mask)
+    go, ld_go = _layer_norm_rows(grad_out)
+    gx = torch.empty((B, D), dtype=torch.float32, device=dev)
+    gm = None if mask is None else torch.empty((B, P, D), dtype=torch.float32, device=dev)
+    gg = torch.empty(D, dtype=torch.float32, device=dev)
+    gb = torch.empty(D, dtype=torch.float32, device=dev)
+    nbytes = lib().dr_layer_norm_workspace_size(B, D)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    check(lib().dr_layer_norm_backward(ptr(xs), ld_x, ptr(rs), ld_r, ptr(_c(gain, torch.float32)),
+                                       ptr(_c(bias, torch.float32)), ptr(ms), ld_m,
+                                       ptr(_c(saved, torch.float32)), ptr(go), ld_go, B, D, P,
+                                       int(bool(relu)), ptr(gx), ptr(gm), ptr(gg), ptr(gb),
+                                       ptr(ws), nbytes, stream_handle(dev)))
+    _post(dev)
+    return gx, gm, gg, gb
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """One launch forward, one plus the finishing launch backward; (mean,
+    rstd) per row is the only saved extra."""
+
+    @staticmethod
+    def forward(ctx, x, gain, bias, residual, mask, eps, relu):
+        out, saved = layer_norm_forward(x, gain, bias, eps, residual, mask, relu)
+        ctx.save_for_backward(x, gain, bias, saved, residual, mask)
+        ctx.relu = relu
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, gain, bias, saved, residual, mask = ctx.saved_tensors
+        gx, gm, gg, gb = layer_norm_backward(x, gain, bias, saved, g_out, residual, mask, ctx.relu)
+        return gx, gg, gb, (None if residual is None else gx), gm, None, None
+
+
+def _layer_norm_torch(x, gain, bias, eps, residual=None, mask=None, relu=False):
+    """The contract of dr_layer_norm_forward as a torch composition (autograd
+    forms the backward): CPU tensors, shapes and dtypes outside the kernels'
+    set, and the DR_LAYER_NORM=torch arm."""
+    s = x if residual is None else x + residual
+    mean = s.mean(-1, keepdim=True)
+    var = ((s - mean) ** 2).mean(-1, keepdim=True)
+    a = gain * (s - mean) / (var + eps) ** 0.5 + bias
+    if relu:
+        a = torch.relu(a)
+    return a if mask is None else a.unsqueeze(1) * mask
+
+
+def layer_norm(x, gain, bias, eps, residual=None, mask=None, relu=False):
+    """Layer normalisation of s = x + residual over the last axis (biased
+    variance, eps inside the root), gain and bias, an optional relu, and an
+    optional product with P masks: x, residual [B, D], gain, bias [D] -> [B, D],
+    or [B, P, D] = a[:, None] * mask with mask [B, P, D] (x is read once for
+    all P outputs).  Gradients for x, residual, gain, bias and mask.  x,
+    residual and mask may be column blocks of wider buffers.  fp32 GPU tensors
+    with D a multiple of 4 in [4, 1024] and P <= 8 run the HIP kernels;
+    anything else (and DR_LAYER_NORM=torch) the torch composition."""
+    if (x.dim() != 2 or gain.shape != x.shape[1:] or bias.shape != x.shape[1:]
+            or (residual is not None and residual.shape != x.shape)
+            or (mask is not None and (mask.dim() != 3 or mask.shape[0] != x.shape[0]
+                                      or mask.shape[2] != x.shape[1]))):
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT,
+                                "layer_norm: x and residual must be [B, D], gain and bias [D] "
+                                "and mask [B, P, D]")
+    if _LAYER_NORM_NATIVE and layer_norm_native_ok(x, gain, bias, residual, mask):
+        return _LayerNormFn.apply(x, gain, bias, residual, mask, eps, relu)
+    return _layer_norm_torch(x, gain, bias, eps, residual, mask, relu)
+
+
+# ---------------------------------------------------------------------------
 # Row-sharded exchange helpers
 # ---------------------------------------------------------------------------
 def partition_by_owner(keys, world, n_dev=None):

@@ -1812,6 +1812,51 @@ int dr_gate_mix_backward(const float* h, int64_t ld_h, const float* gates, const
                          float* grad_z, float* grad_h, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Layer normalisation over the last axis with a residual add in front and a */
+/* relu and P elementwise masks behind, fp32; the forward is one launch, the */
+/* backward one launch plus a small finishing launch (csrc/layer_norm.hip,   */
+/* DESIGN 28).  With s = x + residual (residual nullable):                   */
+/*   mean = mean_D(s)   var = mean_D((s - mean)^2)   rstd = 1 / sqrt(var + eps) */
+/*   xhat = (s - mean) * rstd   u = gain * xhat + bias   a = relu ? max(u, 0) : u */
+/*   out = a [B, D] when mask is NULL (masks must be 1), else                */
+/*   out[b, p, :] = a[b, :] * mask[b, p, :]   [B, P, D]                      */
+/* x, residual [B, >= D] and mask [B, >= P * D] have their own row strides   */
+/* (column blocks of wider buffers); gain, bias [D]; out is contiguous;      */
+/* saved [B, 2] = (mean, rstd) (dr_layer_norm_saved_size bytes) is all the   */
+/* backward keeps.  D a multiple of 4 in [4, 1024], 1 <= P <= 8, B >= 0      */
+/* (B == 0: the forward launches nothing), strides multiples of 4 floats,    */
+/* data pointers 16-byte aligned, eps >= 0; anything else is                 */
+/* DR_INVALID_ARGUMENT.  No allocation, host read, synchronisation or        */
+/* atomics.  A row's out, grad_x and grad_mask are bitwise independent of B, */
+/* of its position and of its neighbours; grad_gain and grad_bias are sums   */
+/* over the batch in an order fixed by (B, D): identical from run to run.    */
+/* ------------------------------------------------------------------------ */
+size_t dr_layer_norm_saved_size(int64_t batch);
+size_t dr_layer_norm_workspace_size(int64_t batch, int64_t width);
+int dr_layer_norm_forward(const float* x, int64_t ld_x, const float* residual /* nullable */,
+                          int64_t ld_residual, const float* gain, const float* bias,
+                          const float* mask /* nullable */, int64_t ld_mask, int64_t batch,
+                          int64_t width, int64_t masks, float eps, int relu, float* out,
+                          float* saved, void* stream);
+/* Backward from grad_out [B, >= P * D] (row stride ld_grad_out; [B, >= D]   */
+/* without masks) and saved:                                                 */
+/*   da = sum_p grad_out_p * mask_p       grad_mask_p = grad_out_p * a       */
+/*   du = da * [u > 0] (relu) or da       dxhat = du * gain                  */
+/*   grad_x = rstd * (dxhat - mean_D(dxhat) - xhat * mean_D(dxhat * xhat))   */
+/*   grad_gain = sum_b du * xhat          grad_bias = sum_b du               */
+/* grad_x [B, D], grad_mask [B, P, D] (NULL exactly when mask is), grad_gain */
+/* and grad_bias [D] are contiguous and written in full; the gradient of     */
+/* residual is grad_x.  workspace: dr_layer_norm_workspace_size(B, D) bytes, */
+/* 16-byte aligned.                                                          */
+int dr_layer_norm_backward(const float* x, int64_t ld_x, const float* residual /* nullable */,
+                           int64_t ld_residual, const float* gain, const float* bias,
+                           const float* mask /* nullable */, int64_t ld_mask, const float* saved,
+                           const float* grad_out, int64_t ld_grad_out, int64_t batch,
+                           int64_t width, int64_t masks, int relu, float* grad_x,
+                           float* grad_mask /* nullable */, float* grad_gain, float* grad_bias,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* String -> id, the step before the lookup.  Strings are one byte buffer    */
 /* plus int64 offsets[n+1] (string i = bytes[offsets[i] .. offsets[i+1])).   */
 /* ------------------------------------------------------------------------ */

@@ -8,11 +8,14 @@ shape plus one negative sample per history position; DR_GRU=torch runs its
 GRUs as torch compositions, the A/B arm) or BST (DIN's batch; DR_MHA=torch
 runs its attention as a torch composition) or MMoE / PLE (DeepFM's synthetic
 batch with two random label columns; DR_GATE_MIX=torch runs the gate softmax
-and expert mixing as a torch composition).  Prints one JSON
+and expert mixing as a torch composition) or MaskNet (DeepFM's synthetic
+batch, serial or --parallel, --dim 16 by default so that the embedding vector
+is 416 wide; DR_LAYER_NORM=torch runs its layer norms as torch compositions).
+Prints one JSON
 line with samples/s and the per-phase split.  A measurement aid for
 SURVEY 8f #4; bench.py's headline metric is the forward lookup.
 
-  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|mmoe|ple|dcn|wdl] [--rows 12500000] [--dim 128]
+  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|mmoe|ple|masknet|dcn|wdl] [--rows 12500000] [--dim 128]
 """
 import argparse
 import json
@@ -29,11 +32,13 @@ sys.path.insert(0, os.path.join(ROOT, "deeprec-1_amd"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dlrm",
-                    choices=["dlrm", "deepfm", "din", "dien", "bst", "mmoe", "ple", "dcn", "wdl"])
+                    choices=["dlrm", "deepfm", "din", "dien", "bst", "mmoe", "ple", "masknet", "dcn",
+                             "wdl"])
+    ap.add_argument("--parallel", action="store_true", help="MaskNet: the parallel model")
     ap.add_argument("--maxlen", type=int, default=100, help="DIN history length bound")
     ap.add_argument("--tables", type=int, default=26)
     ap.add_argument("--rows", type=int, default=12_500_000)
-    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--dim", type=int, default=None, help="128 (MaskNet: 16)")
     ap.add_argument("--batch", type=int, default=None, help="65536 (DIN: 4096)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -51,6 +56,7 @@ def main():
         args.batch = args.batch or 65536
         return wdl(args, dr, mz, dev)
     args.batch = args.batch or 65536
+    args.dim = args.dim or (16 if args.model == "masknet" else 128)
     T, D, B, R = args.tables, args.dim, args.batch, args.rows
     t0 = time.perf_counter()
     evs = []
@@ -63,6 +69,9 @@ def main():
     elif args.model in ("mmoe", "ple"):
         model = mz.MMoE(evs, 13, bf16=args.bf16) if args.model == "mmoe" else mz.PLE(evs, 13)
         model = model.to(dev)
+    elif args.model == "masknet":
+        model = mz.MaskNet(evs, 13, mode="parallel" if args.parallel else "serial",
+                           bf16=args.bf16).to(dev)
     elif args.model == "dcn":     # BASELINE configs[4]: bf16 CrossNet on MFMA, 3 layers
         model = mz.DCNv2(evs, 13, layers=3, deep=(1024, 512), bf16=args.bf16).to(dev)
     else:
@@ -103,6 +112,8 @@ def main():
            "rows": R, "dim": D, "opt": args.opt, "bf16_mlp": args.bf16, "loss": float(loss)}
     if args.model in ("mmoe", "ple"):
         res["gate_mix"] = os.environ.get("DR_GATE_MIX", "native")
+    if args.model == "masknet":
+        res["mode"], res["layer_norm"] = model.mode, os.environ.get("DR_LAYER_NORM", "native")
     print(json.dumps(res), flush=True)
 
 
