@@ -459,6 +459,10 @@ SIGNATURES = {
                                      _I32, _P, _P, _P]),
     "dr_layer_norm_backward": (_I32, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _I64,
                                       _I64, _I64, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dr_cin_workspace_size": (_SZ, [_I64, _I64, _I64, _I64, _I64]),
+    "dr_cin_forward": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
+    "dr_cin_backward": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P,
+                               _SZ, _P]),
     "dr_fingerprint64": (_I32, [_P, _P, _I64, _P, _P]),
     "dr_string_to_hash_bucket_fast": (_I32, [_P, _P, _I64, _I64, _P, _P]),
     "dr_crc32c_extend": (C.c_uint32, [C.c_uint32, _P, _SZ]),

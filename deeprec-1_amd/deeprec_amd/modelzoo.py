@@ -26,6 +26,8 @@ north_star asks.
   csrc/gate_mix.hip (ops.gate_mix; MMoE and PLE classes below).
 * MaskNet: serial and parallel MaskBlocks; every LayerNorm with its relu and
   mask product is csrc/layer_norm.hip (ops.layer_norm; MaskNet class below).
+* xDeepFM: the Compressed Interaction Network on the matrix cores,
+  csrc/cin.hip (ops.cin_layer; CIN and XDeepFM classes below).
 * WDL: modelzoo/WDL/train.py:182-335 (WDL class below).
 * DCN-v2: stacked cross network on the MFMA kernel (DCNv2 class below).
 
@@ -1675,6 +1677,64 @@ class MaskNet(_MultiTaskInput):
 
 def masknet_train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step=None):
     """One MaskNet step: train_step's loss and update (labels [B])."""
+    return train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step)
+
+
+class CIN(torch.nn.Module):
+    """The Compressed Interaction Network (Lian et al., KDD 2018): with x^0 =
+    x0 [B, m, D] and H_0 = m, layer k has H_k = sizes[k - 1] maps
+      x^k[b, h, d] = bias^k[h] + sum_{i < H_{k-1}, j < m} W^k[h, i, j] x^{k-1}[b, i, d] x0[b, j, d]
+    (one ops.cin_layer call; no activation between layers, no split-half) and
+    the output is the sum pooling of every layer over d, concatenated:
+    [B, sum(sizes)]."""
+
+    def __init__(self, m, sizes):
+        super().__init__()
+        self.weights, self.biases = torch.nn.ParameterList(), torch.nn.ParameterList()
+        for hk, hn in zip([m] + list(sizes)[:-1], sizes):
+            bound = float(hk * m) ** -0.5                   # torch.nn.Linear's default range
+            self.weights.append(torch.nn.Parameter(torch.empty(hn, hk, m).uniform_(-bound, bound)))
+            self.biases.append(torch.nn.Parameter(torch.zeros(hn)))
+
+    def forward(self, x0):
+        xk, pooled = x0, []
+        for w, b in zip(self.weights, self.biases):
+            xk = ops.cin_layer(x0, xk, w, b)
+            pooled.append(xk.sum(-1))
+        return torch.cat(pooled, 1)
+
+
+class XDeepFM(_MultiTaskInput):
+    """xDeepFM (Lian et al., KDD 2018) over the DeepFM input: emb = the one-hot
+    lookups [B, T * dim], x = [emb | dense]:
+      logit = linear(x) + dnn(x) + w_cin . CIN(emb.view(B, T, dim))
+      y = sigmoid(logit)                                     -> [B]
+    with linear one Linear to 1, dnn an MLP (relu) with a last 1-unit layer,
+    CIN the class above over the T field embeddings and w_cin a Linear to 1.
+    Every table has the same dim.  On CPU tensors the variables are dense
+    tables, as for DIEN."""
+
+    def __init__(self, evs, dense_dim, cin_sizes=(128, 128), dnn_sizes=(400, 400)):
+        super().__init__(evs, dense_dim)
+        dims = {ev.dim for ev in self.evs}
+        if len(dims) != 1:
+            raise ValueError("XDeepFM: every table must have the same dim (got %s)" % sorted(dims))
+        self.dim = dims.pop()
+        self.linear = torch.nn.Linear(self.n_in, 1)
+        self.dnn = _mlp([self.n_in] + list(dnn_sizes) + [1], last_act=False)
+        self.cin = CIN(len(self.evs), cin_sizes)
+        self.cin_out = torch.nn.Linear(sum(cin_sizes), 1)
+
+    def forward(self, dense, ids):
+        emb = (self.lookup(ids) if ids.is_cuda
+               else _HostTableLookupFn.apply(self.linear.bias, self.evs, ids))
+        x = torch.cat([emb, dense], 1)
+        cin = self.cin(emb.reshape(emb.shape[0], len(self.evs), self.dim))
+        return torch.sigmoid(self.linear(x) + self.dnn(x) + self.cin_out(cin)).squeeze(1)
+
+
+def xdeepfm_train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step=None):
+    """One xDeepFM step: train_step's loss and update (labels [B])."""
     return train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step)
 
 

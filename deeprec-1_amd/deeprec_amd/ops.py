@@ -1581,6 +1581,118 @@ def layer_norm(x, gain, bias, eps, residual=None, mask=None, relu=False):
 
 
 # ---------------------------------------------------------------------------
+# One layer of xDeepFM's Compressed Interaction Network
+# ---------------------------------------------------------------------------
+CIN_MAX = (64, 64, 256)                 # width D, fields m, maps (in and out)
+CIN_TORCH_Z_BYTES = 256 << 20           # the composition's outer product per chunk of B
+# DR_CIN=torch: the torch composition of the same contract on the GPU too (A/B)
+_CIN_NATIVE = os.environ.get("DR_CIN", "native") != "torch"
+
+
+def cin_native_ok(x0, xk, weight):
+    """The kernels take this input: fp32 GPU tensors, x0 [B >= 1, m, D], xk [B,
+    Hk, D], weight [Hn, Hk, m] with D, m <= 64 and Hk, Hn <= 256."""
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in (x0, xk, weight)):
+        return False
+    (B, m, D), Hk, Hn = x0.shape, xk.shape[1], weight.shape[0]
+    return (B >= 1 and 1 <= D <= CIN_MAX[0] and 1 <= m <= CIN_MAX[1]
+            and 1 <= Hk <= CIN_MAX[2] and 1 <= Hn <= CIN_MAX[2])
+
+
+def cin_forward(x0, xk, weight, bias=None):
+    """dr_cin_forward -> out [B, Hn, D]; xk may be x0 itself (the first layer)."""
+    dev = _dev(x0)
+    (B, m, D), Hk, Hn = x0.shape, xk.shape[1], weight.shape[0]
+    x0c = _c(x0, torch.float32)
+    xkc = x0c if xk is x0 else _c(xk, torch.float32)
+    out = torch.empty((B, Hn, D), dtype=torch.float32, device=dev)
+    check(lib().dr_cin_forward(ptr(x0c), ptr(xkc), ptr(_c(weight, torch.float32)),
+                               ptr(None if bias is None else _c(bias, torch.float32)), B, m, Hk,
+                               Hn, D, ptr(out), stream_handle(dev)))
+    _post(dev)
+    return out
+
+
+def cin_backward(x0, xk, weight, grad_out, with_bias=True):
+    """dr_cin_backward -> (grad_xk [B, Hk, D], grad_x0 [B, m, D], grad_weight
+    [Hn, Hk, m], grad_bias [Hn] or None); when xk is x0 the caller adds the
+    first two."""
+    dev = _dev(x0)
+    (B, m, D), Hk, Hn = x0.shape, xk.shape[1], weight.shape[0]
+    x0c = _c(x0, torch.float32)
+    xkc = x0c if xk is x0 else _c(xk, torch.float32)
+    gxk = torch.empty((B, Hk, D), dtype=torch.float32, device=dev)
+    gx0 = torch.empty((B, m, D), dtype=torch.float32, device=dev)
+    gw = torch.empty((Hn, Hk, m), dtype=torch.float32, device=dev)
+    gb = torch.empty(Hn, dtype=torch.float32, device=dev) if with_bias else None
+    nbytes = lib().dr_cin_workspace_size(B, m, Hk, Hn, D)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
+    check(lib().dr_cin_backward(ptr(x0c), ptr(xkc), ptr(_c(weight, torch.float32)),
+                                ptr(_c(grad_out, torch.float32)), B, m, Hk, Hn, D, ptr(gxk),
+                                ptr(gx0), ptr(gw), ptr(gb), ptr(ws), nbytes, stream_handle(dev)))
+    _post(dev)
+    return gxk, gx0, gw, gb
+
+
+class _CinLayerFn(torch.autograd.Function):
+    """One launch forward; backward one launch for the input gradients, one and
+    a finishing launch for the weight and bias gradients.  Nothing is saved
+    but the inputs."""
+
+    @staticmethod
+    def forward(ctx, x0, xk, weight, bias):
+        ctx.save_for_backward(x0, weight) if xk is None else ctx.save_for_backward(x0, weight, xk)
+        ctx.with_bias = bias is not None
+        return cin_forward(x0, x0 if xk is None else xk, weight, bias)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x0, weight = ctx.saved_tensors[:2]
+        first = len(ctx.saved_tensors) == 2
+        xk = x0 if first else ctx.saved_tensors[2]
+        gxk, gx0, gw, gb = cin_backward(x0, xk, weight, g_out, ctx.with_bias)
+        return (gx0 + gxk, None, gw, gb) if first else (gx0, gxk, gw, gb)
+
+
+def _cin_layer_torch(x0, xk, weight, bias=None):
+    """The contract of dr_cin_forward as a torch composition (autograd forms
+    the backward): CPU tensors, other dtypes, shapes outside the kernels' set
+    and the DR_CIN=torch arm.  Z[b, (i, j), d] = xk[b, i, d] x0[b, j, d] is
+    formed by broadcasting and multiplied by W.view(Hn, Hk m), over chunks of
+    B that keep Z under CIN_TORCH_Z_BYTES."""
+    (B, m, D), Hk, Hn = x0.shape, xk.shape[1], weight.shape[0]
+    w = weight.reshape(Hn, Hk * m)
+    step = max(1, CIN_TORCH_Z_BYTES // max(1, Hk * m * D * x0.element_size()))
+    outs = []
+    for lo in range(0, max(B, 1), step):
+        z = (xk[lo:lo + step, :, None, :] * x0[lo:lo + step, None, :, :]).reshape(-1, Hk * m, D)
+        outs.append(torch.matmul(w, z))
+    out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+    return out if bias is None else out + bias[:, None]
+
+
+def cin_layer(x0, xk, weight, bias=None):
+    """One Compressed Interaction Network layer (xDeepFM): out[b, h, d] =
+    bias[h] + sum_{i, j} weight[h, i, j] xk[b, i, d] x0[b, j, d] with x0 [B, m,
+    D], xk [B, Hk, D] (x0 itself in the first layer), weight [Hn, Hk, m], bias
+    [Hn] or None -> [B, Hn, D]; gradients for all of them.  fp32 contiguous
+    GPU tensors with D, m <= 64 and Hk, Hn <= 256 run the HIP kernels, which
+    never store the outer product; anything else (and DR_CIN=torch) the torch
+    composition."""
+    if (x0.dim() != 3 or xk.dim() != 3 or weight.dim() != 3 or xk.shape[0] != x0.shape[0]
+            or xk.shape[2] != x0.shape[2] or weight.shape[1] != xk.shape[1]
+            or weight.shape[2] != x0.shape[1]
+            or (bias is not None and bias.shape != weight.shape[:1])):
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT,
+                                "cin_layer: x0 must be [B, m, D], xk [B, Hk, D], weight [Hn, Hk, "
+                                "m] and bias [Hn]")
+    if (_CIN_NATIVE and cin_native_ok(x0, xk, weight)
+            and (bias is None or (bias.is_cuda and bias.dtype == torch.float32))):
+        return _CinLayerFn.apply(x0, None if xk is x0 else xk, weight, bias)
+    return _cin_layer_torch(x0, xk, weight, bias)
+
+
+# ---------------------------------------------------------------------------
 # Row-sharded exchange helpers
 # ---------------------------------------------------------------------------
 def partition_by_owner(keys, world, n_dev=None):

@@ -1857,6 +1857,42 @@ int dr_layer_norm_backward(const float* x, int64_t ld_x, const float* residual /
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* One layer of xDeepFM's Compressed Interaction Network (Lian et al., KDD   */
+/* 2018), fp32 on the matrix cores (csrc/cin.hip):                */
+/*   out[b, h, d] = bias[h] + sum_{i < Hk, j < m} W[h, i, j] xk[b, i, d] x0[b, j, d] */
+/* x0 [B, m, D] (the field embeddings), xk [B, Hk, D] (the previous layer's  */
+/* maps; the first layer passes x0 again, the same pointer is allowed),      */
+/* weight [Hn, Hk, m], bias [Hn] or NULL, out [B, Hn, D]; all contiguous.    */
+/* 1 <= D <= 64, 1 <= m <= 64, 1 <= Hk, Hn <= 256, B >= 0 (B == 0: no        */
+/* launch); anything else is DR_INVALID_ARGUMENT before any launch.  The     */
+/* outer product over (i, j) is formed in registers and never stored; the    */
+/* forward saves nothing.  No allocation, host read, synchronisation or      */
+/* atomics; every launch captures into a graph.  A sample's out, grad_xk and */
+/* grad_x0 are bitwise independent of B and of its neighbours; grad_weight   */
+/* and grad_bias are sums over the batch in an order fixed by (B D, Hn, Hk,  */
+/* m): identical from run to run.                                            */
+/* ------------------------------------------------------------------------ */
+size_t dr_cin_workspace_size(int64_t batch, int64_t fields, int64_t maps_in, int64_t maps_out,
+                             int64_t width);
+int dr_cin_forward(const float* x0, const float* xk, const float* weight,
+                   const float* bias /* nullable */, int64_t batch, int64_t fields,
+                   int64_t maps_in, int64_t maps_out, int64_t width, float* out, void* stream);
+/* Backward from grad_out [B, Hn, D], re-forming the outer product:          */
+/*   T[b, i, j, d] = sum_h W[h, i, j] grad_out[b, h, d]                      */
+/*   grad_xk[b, i, d] = sum_j T x0[b, j, d]   grad_x0[b, j, d] = sum_i T xk[b, i, d] */
+/*   grad_weight[h, i, j] = sum_{b, d} grad_out[b, h, d] xk[b, i, d] x0[b, j, d] */
+/*   grad_bias[h] = sum_{b, d} grad_out[b, h, d]     (NULL: not written)     */
+/* grad_xk and grad_x0 are two buffers also when xk is x0 (the caller adds   */
+/* them).  workspace: dr_cin_workspace_size bytes (the weight gradient's     */
+/* per-slice partials).  One launch for the input gradients, one and a       */
+/* finishing launch for grad_weight and grad_bias.                           */
+int dr_cin_backward(const float* x0, const float* xk, const float* weight, const float* grad_out,
+                    int64_t batch, int64_t fields, int64_t maps_in, int64_t maps_out,
+                    int64_t width, float* grad_xk, float* grad_x0, float* grad_weight,
+                    float* grad_bias /* nullable */, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* String -> id, the step before the lookup.  Strings are one byte buffer    */
 /* plus int64 offsets[n+1] (string i = bytes[offsets[i] .. offsets[i+1])).   */
 /* ------------------------------------------------------------------------ */

@@ -10,12 +10,14 @@ runs its attention as a torch composition) or MMoE / PLE (DeepFM's synthetic
 batch with two random label columns; DR_GATE_MIX=torch runs the gate softmax
 and expert mixing as a torch composition) or MaskNet (DeepFM's synthetic
 batch, serial or --parallel, --dim 16 by default so that the embedding vector
-is 416 wide; DR_LAYER_NORM=torch runs its layer norms as torch compositions).
+is 416 wide; DR_LAYER_NORM=torch runs its layer norms as torch compositions)
+or xDeepFM (DeepFM's synthetic batch, --dim 16 by default, CIN sizes (128,
+128); DR_CIN=torch runs its CIN layers as torch compositions).
 Prints one JSON
 line with samples/s and the per-phase split.  A measurement aid for
 SURVEY 8f #4; bench.py's headline metric is the forward lookup.
 
-  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|mmoe|ple|masknet|dcn|wdl] [--rows 12500000] [--dim 128]
+  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|mmoe|ple|masknet|xdeepfm|dcn|wdl] [--rows 12500000] [--dim 128]
 """
 import argparse
 import json
@@ -32,13 +34,13 @@ sys.path.insert(0, os.path.join(ROOT, "deeprec-1_amd"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dlrm",
-                    choices=["dlrm", "deepfm", "din", "dien", "bst", "mmoe", "ple", "masknet", "dcn",
-                             "wdl"])
+                    choices=["dlrm", "deepfm", "din", "dien", "bst", "mmoe", "ple", "masknet", "xdeepfm",
+                             "dcn", "wdl"])
     ap.add_argument("--parallel", action="store_true", help="MaskNet: the parallel model")
     ap.add_argument("--maxlen", type=int, default=100, help="DIN history length bound")
     ap.add_argument("--tables", type=int, default=26)
     ap.add_argument("--rows", type=int, default=12_500_000)
-    ap.add_argument("--dim", type=int, default=None, help="128 (MaskNet: 16)")
+    ap.add_argument("--dim", type=int, default=None, help="128 (MaskNet, xDeepFM: 16)")
     ap.add_argument("--batch", type=int, default=None, help="65536 (DIN: 4096)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -56,7 +58,7 @@ def main():
         args.batch = args.batch or 65536
         return wdl(args, dr, mz, dev)
     args.batch = args.batch or 65536
-    args.dim = args.dim or (16 if args.model == "masknet" else 128)
+    args.dim = args.dim or (16 if args.model in ("masknet", "xdeepfm") else 128)
     T, D, B, R = args.tables, args.dim, args.batch, args.rows
     t0 = time.perf_counter()
     evs = []
@@ -72,6 +74,8 @@ def main():
     elif args.model == "masknet":
         model = mz.MaskNet(evs, 13, mode="parallel" if args.parallel else "serial",
                            bf16=args.bf16).to(dev)
+    elif args.model == "xdeepfm":
+        model = mz.XDeepFM(evs, 13).to(dev)
     elif args.model == "dcn":     # BASELINE configs[4]: bf16 CrossNet on MFMA, 3 layers
         model = mz.DCNv2(evs, 13, layers=3, deep=(1024, 512), bf16=args.bf16).to(dev)
     else:
@@ -114,6 +118,8 @@ def main():
         res["gate_mix"] = os.environ.get("DR_GATE_MIX", "native")
     if args.model == "masknet":
         res["mode"], res["layer_norm"] = model.mode, os.environ.get("DR_LAYER_NORM", "native")
+    if args.model == "xdeepfm":
+        res["cin"] = os.environ.get("DR_CIN", "native")
     print(json.dumps(res), flush=True)
 
 
