@@ -28,6 +28,8 @@ north_star asks.
   mask product is csrc/layer_norm.hip (ops.layer_norm; MaskNet class below).
 * xDeepFM: the Compressed Interaction Network on the matrix cores,
   csrc/cin.hip (ops.cin_layer; CIN and XDeepFM classes below).
+* CAN: the Co-Action Network on DIN's inputs; its per-sample micro-MLP over
+  the history is csrc/co_action.hip (ops.co_action; CAN class below).
 * WDL: modelzoo/WDL/train.py:182-335 (WDL class below).
 * DCN-v2: stacked cross network on the MFMA kernel (DCNv2 class below).
 
@@ -1457,6 +1459,77 @@ def bst_train_step(model, batch, dense_opt, ev_opt, global_step=None, world=1, g
                    staged=False):
     """One BST step: DIN's loss and update (din_train_step) on the BST model,
     world > 1 included."""
+    return din_train_step(model, batch, dense_opt, ev_opt, global_step, world, group, staged)
+
+
+class CAN(torch.nn.Module):
+    """Co-Action Network (the reference zoo's CAN) on DIN's inputs: one merged
+    item lookup over [target | history]; the target's mid and cat ids also look
+    up, in two further variables of dim P, the weights of a micro-MLP of
+    `widths` (ops.co_action_param_len(widths, orders) floats), which
+    ops.co_action applies to the powers 1..orders of the history's mid and cat
+    halves (one HIP kernel each way per half on the GPU, reading the column
+    blocks of both lookups in place).  The two co-action vectors join [uid,
+    item_eb, his_sum, item_eb * his_sum] (his_sum as DIEN forms it) into DIN's
+    head: inference-form batch normalisation, 200 Dice, 80 Dice, 2, softmax +
+    1e-8.  forward returns y_hat [B, 2].  On CPU tensors the five variables are
+    dense tables, as for DIEN."""
+
+    def __init__(self, uid_ev, mid_ev, cat_ev, mid_mlp_ev, cat_mlp_ev, widths=(16, 8, 4),
+                 orders=3):
+        super().__init__()
+        self.widths, self.orders = tuple(int(d) for d in widths), int(orders)
+        self.P = ops.co_action_param_len(self.widths, self.orders)
+        if not mid_ev.dim == cat_ev.dim == self.widths[0]:
+            raise ValueError("CAN: the mid and cat tables must have dim widths[0] = %d (got %d, %d)"
+                             % (self.widths[0], mid_ev.dim, cat_ev.dim))
+        if not mid_mlp_ev.dim == cat_mlp_ev.dim == self.P:
+            raise ValueError("CAN: the weight tables must have dim %d, the weights of widths %s "
+                             "(got %d, %d)" % (self.P, self.widths, mid_mlp_ev.dim,
+                                               cat_mlp_ev.dim))
+        self.evs = [uid_ev, mid_ev, cat_ev, mid_mlp_ev, cat_mlp_ev]
+        H = 2 * mid_ev.dim
+        n_in = uid_ev.dim + 3 * H + 2 * self.orders * sum(self.widths[1:])
+        self.bn1_gamma = torch.nn.Parameter(torch.ones(n_in))
+        self.bn1_beta = torch.nn.Parameter(torch.zeros(n_in))
+        self.dnn1 = torch.nn.Linear(n_in, 200)
+        self.dice_1 = Dice(200)
+        self.dnn2 = torch.nn.Linear(200, 80)
+        self.dice_2 = Dice(80)
+        self.dnn3 = torch.nn.Linear(80, 2)
+        self.uid_lookup = _OneHotLookup([uid_ev])
+        self.item_lookup = _OneHotLookup([mid_ev, cat_ev])
+        self.mlp_lookup = _OneHotLookup([mid_mlp_ev, cat_mlp_ev])
+
+    def _lookup(self, lookup, ids):
+        if ids.is_cuda:
+            return lookup(ids)
+        return _HostTableLookupFn.apply(self.bn1_beta, lookup.evs, ids)
+
+    def forward(self, uids, mids, cats, mid_his, cat_his, mask):
+        B, T = mid_his.shape
+        D, P = self.widths[0], self.P
+        uid_e = self._lookup(self.uid_lookup, uids.reshape(1, B))
+        ids = torch.stack([torch.cat([mids, mid_his.reshape(-1)]),
+                           torch.cat([cats, cat_his.reshape(-1)])])
+        allv = self._lookup(self.item_lookup, ids)                                 # [B + B T, 2D]
+        item_eb = allv[:B]
+        his = allv[B:].view(B, T, -1)                                              # [B, T, 2D]
+        w = self._lookup(self.mlp_lookup, torch.stack([mids, cats]))               # [B, 2P]
+        co = torch.cat([ops.co_action(w[:, :P], his[..., :D], mask, self.widths, self.orders),
+                        ops.co_action(w[:, P:], his[..., D:], mask, self.widths, self.orders)], 1)
+        his_sum = his.sum(1)
+        inp = torch.cat([uid_e, item_eb, his_sum, item_eb * his_sum, co], -1)
+        bn = inp * DIEN.BN_SCALE * self.bn1_gamma + self.bn1_beta
+        x = self.dice_1(self.dnn1(bn))
+        x = self.dice_2(self.dnn2(x))
+        return torch.softmax(self.dnn3(x), -1) + 1e-8
+
+
+def can_train_step(model, batch, dense_opt, ev_opt, global_step=None, world=1, group=None,
+                   staged=False):
+    """One CAN step: DIN's loss and update (din_train_step) on the CAN model
+    and its five variables, world > 1 included."""
     return din_train_step(model, batch, dense_opt, ev_opt, global_step, world, group, staged)
 
 

@@ -1693,6 +1693,150 @@ def cin_layer(x0, xk, weight, bias=None):
 
 
 # ---------------------------------------------------------------------------
+# CAN's co-action unit: a per-sample micro-MLP over a history
+# ---------------------------------------------------------------------------
+CO_ACTION_MAX = (3, 32, 4)              # layers, width, orders
+# DR_CO_ACTION=torch: the torch composition of the same contract on the GPU too (A/B)
+_CO_ACTION_NATIVE = os.environ.get("DR_CO_ACTION", "native") != "torch"
+
+
+def co_action_param_len(widths, orders, bias=False, order_indep=False):
+    """P: the floats of one sample's weights."""
+    per = sum(a * b + (b if bias else 0) for a, b in zip(widths[:-1], widths[1:]))
+    return per * (orders if order_indep else 1)
+
+
+def co_action_native_ok(param, his, mask, widths, orders):
+    """The kernels take this input: fp32 GPU tensors, B >= 1, T >= 1, 1 to 3
+    layers of widths that are multiples of 4 in [4, 32], orders in [1, 4]."""
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in (param, his, mask)):
+        return False
+    L, D, O = CO_ACTION_MAX
+    return (his.shape[0] >= 1 and his.shape[1] >= 1 and 2 <= len(widths) <= L + 1
+            and all(4 <= d <= D and d % 4 == 0 for d in widths) and 1 <= orders <= O
+            and his.numel() < 2 ** 31)
+
+
+def _co_action_rows(param, his):
+    """param and his as the kernels read them: (param, ld_param, his, ld_his),
+    unchanged when they are fp32 views with a contiguous last dimension, one
+    row stride that is a multiple of 4 and a 16-byte aligned start (the column
+    blocks of a merged lookup), contiguous copies otherwise."""
+    B, T, d0 = his.shape
+    if not (param.dtype == torch.float32 and param.stride(1) == 1 and param.stride(0) % 4 == 0
+            and param.stride(0) >= param.shape[1] and param.data_ptr() % 16 == 0):
+        param = _c(param, torch.float32)
+    if not (his.dtype == torch.float32 and his.stride(2) == 1 and his.stride(1) % 4 == 0
+            and his.stride(1) >= d0 and his.stride(0) == T * his.stride(1)
+            and his.data_ptr() % 16 == 0):
+        his = _c(his, torch.float32)
+    return param, param.stride(0), his, his.stride(1)
+
+
+def _co_action_widths(widths):
+    return (C.c_int * len(widths))(*[int(d) for d in widths])
+
+
+def co_action_forward(param, his, mask, widths, orders, bias=False, order_indep=False):
+    """dr_co_action_forward -> out [B, orders * sum(widths[1:])]."""
+    dev = _dev(his)
+    B, T, _ = his.shape
+    param, ld_p, his, ld_h = _co_action_rows(param, his)
+    out = torch.empty((B, orders * sum(widths[1:])), dtype=torch.float32, device=dev)
+    check(lib().dr_co_action_forward(ptr(param), ld_p, ptr(his), ld_h, ptr(_c(mask, torch.float32)),
+                                     B, T, _co_action_widths(widths), len(widths) - 1, orders,
+                                     int(bias), int(order_indep), ptr(out), stream_handle(dev)))
+    _post(dev)
+    return out
+
+
+def co_action_backward(param, his, mask, grad_out, widths, orders, bias=False, order_indep=False):
+    """dr_co_action_backward -> (grad_his [B, T, d0], grad_param [B, P]), both
+    dense and written in full."""
+    dev = _dev(his)
+    B, T, d0 = his.shape
+    param, ld_p, his, ld_h = _co_action_rows(param, his)
+    gh = torch.empty((B, T, d0), dtype=torch.float32, device=dev)
+    gp = torch.empty((B, param.shape[1]), dtype=torch.float32, device=dev)
+    check(lib().dr_co_action_backward(ptr(param), ld_p, ptr(his), ld_h,
+                                      ptr(_c(mask, torch.float32)),
+                                      ptr(_c(grad_out, torch.float32)), B, T,
+                                      _co_action_widths(widths), len(widths) - 1, orders, int(bias),
+                                      int(order_indep), ptr(gh), ptr(gp), stream_handle(dev)))
+    _post(dev)
+    return gh, gp
+
+
+class _CoActionFn(torch.autograd.Function):
+    """One launch each way; nothing is saved but the inputs (the backward
+    recomputes the activations tile by tile)."""
+
+    @staticmethod
+    def forward(ctx, param, his, mask, widths, orders, bias, order_indep):
+        ctx.save_for_backward(param, his, mask)
+        ctx.cfg = (widths, orders, bias, order_indep)
+        return co_action_forward(param, his, mask, *ctx.cfg)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        param, his, mask = ctx.saved_tensors
+        gh, gp = co_action_backward(param, his, mask, g_out, *ctx.cfg)
+        return gp, gh, None, None, None, None, None
+
+
+def _co_action_torch(param, his, mask, widths, orders, bias=False, order_indep=False):
+    """The contract of dr_co_action_forward as a torch composition (autograd
+    forms the backward): CPU tensors, other dtypes, widths outside the kernels'
+    set and the DR_CO_ACTION=torch arm.  A position with mask 0 is replaced by
+    zeros before it is used, as the kernels skip it."""
+    B = his.shape[0]
+    live = (mask != 0).unsqueeze(-1)
+    his = torch.where(live, his, torch.zeros_like(his))
+    m = mask.to(his.dtype).unsqueeze(-1)
+    outs, at = [], 0
+    for p in range(1, orders + 1):
+        if not order_indep:
+            at = 0
+        h = his ** p
+        for j, (a, b) in enumerate(zip(widths[:-1], widths[1:])):
+            h = torch.bmm(h, param[:, at:at + a * b].reshape(B, a, b))
+            at += a * b
+            if bias:
+                h = h + param[:, None, at:at + b]
+                at += b
+            if j + 2 < len(widths):
+                h = torch.tanh(h)
+            outs.append((h * m).sum(1))
+    return torch.cat(outs, 1)
+
+
+def co_action(param, his, mask, widths=(16, 8, 4), orders=3, bias=False, order_indep=False):
+    """CAN's co-action unit (the reference's gen_coaction, mode "can"): param
+    [B, P] holds, per sample, the weights of a small MLP of widths (d0, ...,
+    dL) -- per set, for every layer W_j [d(j-1), d(j)] row-major, then b_j if
+    bias; one set, or one per order with order_indep.  For p = 1..orders the
+    MLP (tanh between the layers, none after the last) runs on his ** p, his
+    [B, T, d0], and every layer's activations are summed over the positions
+    with mask [B, T] -> [B, orders * sum(widths[1:])]; a position with mask 0
+    is not read.  Gradients for param and his.  param and his may be column
+    blocks of wider buffers.  fp32 GPU tensors with at most 3 layers, widths
+    that are multiples of 4 up to 32 and orders <= 4 run one HIP kernel each
+    way; anything else (and DR_CO_ACTION=torch) the torch composition."""
+    widths = tuple(int(d) for d in widths)
+    if (his.dim() != 3 or param.dim() != 2 or mask.dim() != 2 or len(widths) < 2 or orders < 1
+            or min(widths) < 1 or his.shape[2] != widths[0] or mask.shape != his.shape[:2]
+            or param.shape != (his.shape[0],
+                               co_action_param_len(widths, orders, bias, order_indep))):
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT,
+                                "co_action: his must be [B, T, widths[0]], mask [B, T] and param "
+                                "[B, P] with P the weights of the widths, orders and sets")
+    if _CO_ACTION_NATIVE and co_action_native_ok(param, his, mask, widths, orders):
+        return _CoActionFn.apply(param, his, mask, widths, int(orders), bool(bias),
+                                 bool(order_indep))
+    return _co_action_torch(param, his, mask, widths, int(orders), bias, order_indep)
+
+
+# ---------------------------------------------------------------------------
 # Row-sharded exchange helpers
 # ---------------------------------------------------------------------------
 def partition_by_owner(keys, world, n_dev=None):

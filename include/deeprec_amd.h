@@ -1893,7 +1893,43 @@ int dr_cin_backward(const float* x0, const float* xk, const float* weight, const
                     void* stream);
 
 /* ------------------------------------------------------------------------ */
-/* String -> id, the step before the lookup.  Strings are one byte buffer    */
+/* CAN's co-action unit (Bian et al., WSDM 2022; the reference's             */
+/* gen_coaction, mode "can"): a per-sample micro-MLP over the positions of a */
+/* history, fp32 on the matrix cores (csrc/co_action.hip).        */
+/*   widths = (d0, ..., dL), layers = L in [1, 3], every d a multiple of 4   */
+/*   in [4, 32]; orders in [1, 4]; bias, order_indep in {0, 1};              */
+/*   sets = order_indep ? orders : 1;                                        */
+/*   P = sets * sum_j (d[j-1] d[j] + (bias ? d[j] : 0))                      */
+/*   param [B, P], row stride ld_param: per set, for j = 1..L: W_j row-major */
+/*   [d[j-1], d[j]], then b_j [d[j]] if bias                                 */
+/*   his [B, T, d0], position stride ld_his (sample stride T ld_his);        */
+/*   mask [B, T] fp32, contiguous                                            */
+/*   for p = 1..orders: a = his ** p; (W, b) = set p - 1 or set 0            */
+/*     for j = 1..L: a = a W_j (+ b_j); j < L: a = tanh(a); seq[p][j] = a    */
+/*   out [B, orders * sum_{j>=1} d_j] = sum_t mask[b, t] concat_{p, j} seq   */
+/* A position with mask 0 is not read.  Strides are multiples of 4 floats    */
+/* that hold a row; param, his, out and the gradients are 16-byte aligned.   */
+/* B T d0 < 2^31; B == 0: no launch.  Anything else is DR_INVALID_ARGUMENT   */
+/* before any launch.  One launch each way, no workspace, no allocation,     */
+/* host read, synchronisation or atomics; both capture into a graph.  One    */
+/* wave owns a sample: its results are bitwise independent of the batch and  */
+/* identical from run to run.                                                */
+/* ------------------------------------------------------------------------ */
+int dr_co_action_forward(const float* param, int64_t ld_param, const float* his, int64_t ld_his,
+                         const float* mask, int64_t batch, int64_t positions, const int* widths,
+                         int layers, int orders, int bias, int order_indep, float* out,
+                         void* stream);
+/* Backward from grad_out [B, orders * sum d_j] (contiguous), recomputing    */
+/* the activations from his and param: grad_his [B, T, d0] and grad_param    */
+/* [B, P], both contiguous and written in full (exact zeros where mask is 0  */
+/* and for a sample without a live position).                                */
+int dr_co_action_backward(const float* param, int64_t ld_param, const float* his, int64_t ld_his,
+                          const float* mask, const float* grad_out, int64_t batch,
+                          int64_t positions, const int* widths, int layers, int orders, int bias,
+                          int order_indep, float* grad_his, float* grad_param, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* String -> id, the step before the lookup. Strings are one byte buffer    */
 /* plus int64 offsets[n+1] (string i = bytes[offsets[i] .. offsets[i+1])).   */
 /* ------------------------------------------------------------------------ */
 /* farmhash Fingerprint64 (core/platform/fingerprint.h:80-88; the Fingerprint */

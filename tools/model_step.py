@@ -12,12 +12,14 @@ and expert mixing as a torch composition) or MaskNet (DeepFM's synthetic
 batch, serial or --parallel, --dim 16 by default so that the embedding vector
 is 416 wide; DR_LAYER_NORM=torch runs its layer norms as torch compositions)
 or xDeepFM (DeepFM's synthetic batch, --dim 16 by default, CIN sizes (128,
-128); DR_CIN=torch runs its CIN layers as torch compositions).
+128); DR_CIN=torch runs its CIN layers as torch compositions) or CAN (DIN's
+batch at dim 16 plus two weight tables of dim 160; DR_CO_ACTION=torch runs its
+co-action units as torch compositions).
 Prints one JSON
 line with samples/s and the per-phase split.  A measurement aid for
 SURVEY 8f #4; bench.py's headline metric is the forward lookup.
 
-  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|mmoe|ple|masknet|xdeepfm|dcn|wdl] [--rows 12500000] [--dim 128]
+  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|can|mmoe|ple|masknet|xdeepfm|dcn|wdl] [--rows 12500000] [--dim 128]
 """
 import argparse
 import json
@@ -34,8 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "deeprec-1_amd"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dlrm",
-                    choices=["dlrm", "deepfm", "din", "dien", "bst", "mmoe", "ple", "masknet", "xdeepfm",
-                             "dcn", "wdl"])
+                    choices=["dlrm", "deepfm", "din", "dien", "bst", "can", "mmoe", "ple", "masknet",
+                             "xdeepfm", "dcn", "wdl"])
     ap.add_argument("--parallel", action="store_true", help="MaskNet: the parallel model")
     ap.add_argument("--maxlen", type=int, default=100, help="DIN history length bound")
     ap.add_argument("--tables", type=int, default=26)
@@ -51,7 +53,7 @@ def main():
     from deeprec_amd import modelzoo as mz
     dr.load()
     dev = torch.device("cuda", 0)
-    if args.model in ("din", "dien", "bst"):
+    if args.model in ("din", "dien", "bst", "can"):
         args.batch = args.batch or 4096
         return din(args, dr, mz, dev)
     if args.model == "wdl":
@@ -178,18 +180,22 @@ def din(args, dr, mz, dev):
     """DIN step: B samples, history lengths U[1, maxlen] padded to the batch
     max (prepare_data, modelzoo/DIN/train.py:24-88), vocab 5e5 users / 4e5
     items / 2e3 categories, dim 18, Adam.  DIEN: the
-    same batch plus one negative item / category per history position."""
-    dien = args.model == "dien"
-    B, T, D = args.batch, args.maxlen, 18
+    same batch plus one negative item / category per history position.  CAN:
+    dim 16 (the micro-MLP's input width) and the item / category weight tables
+    of dim 160 (widths (16, 8, 4))."""
+    dien, can = args.model == "dien", args.model == "can"
+    B, T, D = args.batch, args.maxlen, 16 if can else 18
     R = (500_000, 400_000, 2_000)
     evs = []
-    for i, r in enumerate(R):
-        ev = dr.EmbeddingVariable("din%d" % i, D, 0.0, capacity=r + (1 << 16), device=dev)
+    for i, r in enumerate(R + (R[1:] if can else ())):
+        ev = dr.EmbeddingVariable("din%d" % i, 160 if i >= 3 else D, 0.0, capacity=r + (1 << 16),
+                                  device=dev)
         ev.insert_synthetic(0, r, seed=700 + i)
         evs.append(ev)
     bst = args.model == "bst"
-    model = (mz.DIEN if dien else mz.BST if bst else mz.DIN)(*evs).to(dev)
-    step = mz.dien_train_step if dien else mz.bst_train_step if bst else mz.din_train_step
+    model = (mz.DIEN if dien else mz.BST if bst else mz.CAN if can else mz.DIN)(*evs).to(dev)
+    step = (mz.dien_train_step if dien else mz.bst_train_step if bst else mz.can_train_step if can
+            else mz.din_train_step)
     dopt = torch.optim.Adam(model.parameters(), lr=0.001)
     eopt = dr.AdamOptimizer(0.001)
     g = torch.Generator(device=dev)
@@ -220,7 +226,7 @@ def din(args, dr, mz, dev):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     dr.status_check(dev)
-    nnz = sum(int(b[5].numel()) * (4 if dien else 2) + 3 * B for b in batches) / 4
+    nnz = sum(int(b[5].numel()) * (4 if dien else 2) + (5 if can else 3) * B for b in batches) / 4
     res = {"model": args.model, "samples_per_s": round(B * args.steps / el, 1),
            "lookups_per_s": round(nnz * args.steps / el, 1),
            "ms_per_step": round(el / args.steps * 1e3, 3), "batch": B, "maxlen": T,
@@ -229,6 +235,8 @@ def din(args, dr, mz, dev):
         res["gru"] = os.environ.get("DR_GRU", "native")
     if bst:
         res["mha"] = os.environ.get("DR_MHA", "native")
+    if can:
+        res["co_action"] = os.environ.get("DR_CO_ACTION", "native")
     print(json.dumps(res), flush=True)
 
 
