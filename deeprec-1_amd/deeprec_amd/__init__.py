@@ -21,8 +21,8 @@ from .kv_variable_ops import (AdaptiveEmbeddingVariable, CBFFilter, CounterFilte
                               StorageType, flush_releases, get_adaptive_embedding_variable,
                               get_embedding_variable,
                               get_multihash_variable, read_only_lookups, read_only_serves_tier)
-from .ops import (cin_layer, co_action, gate_mix, gru_sequence, layer_norm, multihead_attention,
-                  set_validate, status_check)
+from .ops import (bilinear_interaction, cin_layer, co_action, gate_mix, gru_sequence, layer_norm,
+                  multihead_attention, set_validate, status_check)
 from .string_ops import StringTensor, string_to_hash_bucket_fast
 from .training import (AdagradDecayOptimizer, AdagradOptimizer, AdamAsyncOptimizer, AdamOptimizer,
                        FtrlOptimizer, GradientDescentOptimizer)
@@ -39,5 +39,5 @@ __all__ = [
     "read_only_serves_tier", "MultiHashVariable", "MultiHashVariableConfig",
     "get_multihash_variable", "AdaptiveEmbeddingVariable", "get_adaptive_embedding_variable",
     "adaptive_embedding_lookup_sparse", "gru_sequence", "multihead_attention", "gate_mix",
-    "layer_norm", "cin_layer", "co_action",
+    "layer_norm", "cin_layer", "co_action", "bilinear_interaction",
 ]

@@ -467,6 +467,10 @@ SIGNATURES = {
                                     _P, _P]),
     "dr_co_action_backward": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _P, _I32, _I32, _I32,
                                      _I32, _P, _P, _P]),
+    "dr_bilinear_workspace_size": (_SZ, [_I32, _I64, _I64, _I64]),
+    "dr_bilinear_forward": (_I32, [_P, _P, _P, _I32, _I64, _I64, _I64, _P, _P]),
+    "dr_bilinear_backward": (_I32, [_P, _P, _P, _P, _I32, _I64, _I64, _I64, _P, _P, _P, _P, _SZ,
+                                    _P]),
     "dr_fingerprint64": (_I32, [_P, _P, _I64, _P, _P]),
     "dr_string_to_hash_bucket_fast": (_I32, [_P, _P, _I64, _I64, _P, _P]),
     "dr_crc32c_extend": (C.c_uint32, [C.c_uint32, _P, _SZ]),

@@ -30,6 +30,9 @@ north_star asks.
   csrc/cin.hip (ops.cin_layer; CIN and XDeepFM classes below).
 * CAN: the Co-Action Network on DIN's inputs; its per-sample micro-MLP over
   the history is csrc/co_action.hip (ops.co_action; CAN class below).
+* FiBiNET: SENET field weights and the bilinear interaction over every pair of
+  fields, csrc/bilinear.hip (ops.bilinear_interaction; SENet and FiBiNET
+  classes below).
 * WDL: modelzoo/WDL/train.py:182-335 (WDL class below).
 * DCN-v2: stacked cross network on the MFMA kernel (DCNv2 class below).
 
@@ -1808,6 +1811,71 @@ class XDeepFM(_MultiTaskInput):
 
 def xdeepfm_train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step=None):
     """One xDeepFM step: train_step's loss and update (labels [B])."""
+    return train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step)
+
+
+class SENet(torch.nn.Module):
+    """FiBiNET's squeeze-and-excitation over the fields: x [B, m, D] ->
+    z = mean (pool "max": max) over D, a = relu(W2 relu(W1 z)) with bias-free
+    Linears m -> max(1, m // reduction) -> m.  Returns the field weights a
+    [B, m]; the product a_i x_i is left to ops.bilinear_interaction(scale=a)."""
+
+    def __init__(self, m, reduction=3, pool="mean"):
+        super().__init__()
+        if pool not in ("mean", "max"):
+            raise ValueError("SENet: pool is 'mean' or 'max' (got %r)" % (pool,))
+        self.pool = pool
+        hidden = max(1, m // reduction)
+        self.squeeze = torch.nn.Linear(m, hidden, bias=False)
+        self.excite = torch.nn.Linear(hidden, m, bias=False)
+
+    def forward(self, x):
+        z = x.mean(-1) if self.pool == "mean" else x.max(-1).values
+        return torch.relu(self.excite(torch.relu(self.squeeze(z))))
+
+
+class FiBiNET(_MultiTaskInput):
+    """FiBiNET (Huang et al., RecSys 2019) over the DeepFM input: emb = the
+    one-hot lookups [B, T * dim], e = emb.view(B, T, dim), x = [emb | dense]:
+      p = bilinear(e, W_p)                  q = bilinear(e, W_q, scale=SENet(e))
+      y = sigmoid(linear(x) + dnn([p | q | dense]))          -> [B]
+    with bilinear ops.bilinear_interaction of the given kind over the T (T - 1)
+    / 2 pairs (csrc/bilinear.hip; the SENET weights are applied inside it),
+    linear one Linear to 1 and dnn an MLP (relu) with a last 1-unit layer.
+    Every table has the same dim.  On CPU tensors the variables are dense
+    tables, as for DIEN."""
+
+    def __init__(self, evs, dense_dim, kind="interaction", reduction=3,
+                 dnn_sizes=(400, 400, 400)):
+        super().__init__(evs, dense_dim)
+        dims = {ev.dim for ev in self.evs}
+        if len(dims) != 1:
+            raise ValueError("FiBiNET: every table must have the same dim (got %s)" % sorted(dims))
+        if kind not in ops.BILINEAR_KINDS:
+            raise ValueError("FiBiNET: kind is one of %s (got %r)" % (ops.BILINEAR_KINDS, kind))
+        self.dim, self.kind = dims.pop(), kind
+        T = len(self.evs)
+        pairs = T * (T - 1) // 2
+        n_w = {"all": 1, "each": T, "interaction": pairs}[kind]
+        bound = float(self.dim) ** -0.5                      # torch.nn.Linear's default range
+        self.w_p = torch.nn.Parameter(torch.empty(n_w, self.dim, self.dim).uniform_(-bound, bound))
+        self.w_q = torch.nn.Parameter(torch.empty(n_w, self.dim, self.dim).uniform_(-bound, bound))
+        self.senet = SENet(T, reduction)
+        self.linear = torch.nn.Linear(self.n_in, 1)
+        self.dnn = _mlp([2 * pairs * self.dim + dense_dim] + list(dnn_sizes) + [1], last_act=False)
+
+    def forward(self, dense, ids):
+        emb = (self.lookup(ids) if ids.is_cuda
+               else _HostTableLookupFn.apply(self.linear.bias, self.evs, ids))
+        e = emb.reshape(emb.shape[0], len(self.evs), self.dim)
+        p = ops.bilinear_interaction(e, self.w_p, self.kind)
+        q = ops.bilinear_interaction(e, self.w_q, self.kind, scale=self.senet(e))
+        deep = self.dnn(torch.cat([p.flatten(1), q.flatten(1), dense], 1))
+        return torch.sigmoid(self.linear(torch.cat([emb, dense], 1)) + deep).squeeze(1)
+
+
+def fibinet_train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step=None):
+    """One FiBiNET step: train_step's loss and update (labels [B])."""
     return train_step(model, dense, ids, labels, dense_opt, ev_opt, global_step)
 
 

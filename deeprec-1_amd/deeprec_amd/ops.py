@@ -1837,6 +1837,117 @@ def co_action(param, his, mask, widths=(16, 8, 4), orders=3, bias=False, order_i
 
 
 # ---------------------------------------------------------------------------
+# FiBiNET's bilinear interaction over every pair of fields
+# ---------------------------------------------------------------------------
+BILINEAR_MAX = (64, 64)                 # fields m, width D
+BILINEAR_KINDS = ("all", "each", "interaction")
+# DR_BILINEAR=torch: the torch composition of the same contract on the GPU too (A/B)
+_BILINEAR_NATIVE = os.environ.get("DR_BILINEAR", "native") != "torch"
+
+
+def bilinear_native_ok(x, weight, scale=None):
+    """The kernels take this input: fp32 GPU tensors, x [B >= 1, m, D] with
+    2 <= m <= 64 and 1 <= D <= 64, weight [*, D, D], scale [B, m] or None."""
+    ts = (x, weight) if scale is None else (x, weight, scale)
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    B, m, D = x.shape
+    return B >= 1 and 2 <= m <= BILINEAR_MAX[0] and 1 <= D <= BILINEAR_MAX[1]
+
+
+def bilinear_forward(x, weight, kind, scale=None):
+    """dr_bilinear_forward -> out [B, m (m - 1) / 2, D]."""
+    dev = _dev(x)
+    B, m, D = x.shape
+    out = torch.empty((B, m * (m - 1) // 2, D), dtype=torch.float32, device=dev)
+    check(lib().dr_bilinear_forward(ptr(_c(x, torch.float32)),
+                                    ptr(None if scale is None else _c(scale, torch.float32)),
+                                    ptr(_c(weight, torch.float32)), BILINEAR_KINDS.index(kind), B,
+                                    m, D, ptr(out), stream_handle(dev)))
+    _post(dev)
+    return out
+
+
+def bilinear_backward(x, weight, kind, grad_out, scale=None):
+    """dr_bilinear_backward -> (grad_x [B, m, D], grad_scale [B, m] or None,
+    grad_weight of weight's shape)."""
+    dev = _dev(x)
+    B, m, D = x.shape
+    k = BILINEAR_KINDS.index(kind)
+    gx = torch.empty((B, m, D), dtype=torch.float32, device=dev)
+    gs = None if scale is None else torch.empty((B, m), dtype=torch.float32, device=dev)
+    gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=dev)
+    nbytes = lib().dr_bilinear_workspace_size(k, B, m, D)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
+    check(lib().dr_bilinear_backward(ptr(_c(x, torch.float32)),
+                                     ptr(None if scale is None else _c(scale, torch.float32)),
+                                     ptr(_c(weight, torch.float32)),
+                                     ptr(_c(grad_out, torch.float32)), k, B, m, D, ptr(gx),
+                                     ptr(gs), ptr(gw), ptr(ws), nbytes, stream_handle(dev)))
+    _post(dev)
+    return gx, gs, gw
+
+
+class _BilinearFn(torch.autograd.Function):
+    """One launch forward; backward one launch for grad_x and grad_scale, one
+    and a finishing launch for grad_weight.  Nothing is saved but the inputs."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale, kind):
+        ctx.save_for_backward(x, weight) if scale is None else ctx.save_for_backward(x, weight,
+                                                                                     scale)
+        ctx.kind = kind
+        return bilinear_forward(x, weight, kind, scale)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, weight = ctx.saved_tensors[:2]
+        scale = ctx.saved_tensors[2] if len(ctx.saved_tensors) == 3 else None
+        gx, gs, gw = bilinear_backward(x, weight, ctx.kind, g_out, scale)
+        return gx, gw, gs, None
+
+
+def _bilinear_torch(x, weight, kind, scale=None):
+    """The contract of dr_bilinear_forward as a torch composition (autograd
+    forms the backward): CPU tensors, other dtypes, shapes outside the
+    kernels' set and the DR_BILINEAR=torch arm."""
+    m = x.shape[1]
+    idx = torch.triu_indices(m, m, 1, device=x.device)
+    v = x if scale is None else x * scale.unsqueeze(-1)
+    if kind == "interaction":
+        u = torch.matmul(v[:, idx[0]].unsqueeze(2), weight).squeeze(2)
+    else:
+        # weight [1 or m, D, D] broadcasts over the fields
+        u = torch.matmul(v.unsqueeze(2), weight).squeeze(2)[:, idx[0]]
+    return u * v[:, idx[1]]
+
+
+def bilinear_interaction(x, weight, kind="interaction", scale=None):
+    """FiBiNET's bilinear interaction: x [B, m, D] field embeddings, v = x or
+    scale[:, :, None] * x with scale [B, m] (SENET's weights), and for every
+    pair i < j in itertools.combinations' order out[b, p, :] = (v_i W) * v_j
+    -> [B, m (m - 1) / 2, D], with W = weight[0] (kind "all", weight [1, D,
+    D]), weight[i] ("each", [m, D, D]) or weight[p] ("interaction", [P, D,
+    D]).  Gradients for x, weight and scale.  fp32 contiguous GPU tensors with
+    2 <= m <= 64 and D <= 64 run the HIP kernels, which write the output once
+    and store nothing else; anything else (and DR_BILINEAR=torch) the torch
+    composition."""
+    ok = kind in BILINEAR_KINDS and x.dim() == 3 and weight.dim() == 3 and x.shape[1] >= 2
+    if ok:
+        B, m, D = x.shape
+        n = {"all": 1, "each": m, "interaction": m * (m - 1) // 2}[kind]
+        ok = tuple(weight.shape) == (n, D, D) and (scale is None or tuple(scale.shape) == (B, m))
+    if not ok:
+        raise _lib.DeepRecError(_lib.INVALID_ARGUMENT,
+                                "bilinear_interaction: x must be [B, m >= 2, D], scale [B, m] and "
+                                "weight [1, D, D] (kind all), [m, D, D] (each) or [m (m - 1) / 2, "
+                                "D, D] (interaction)")
+    if _BILINEAR_NATIVE and bilinear_native_ok(x, weight, scale):
+        return _BilinearFn.apply(x, weight, scale, kind)
+    return _bilinear_torch(x, weight, kind, scale)
+
+
+# ---------------------------------------------------------------------------
 # Row-sharded exchange helpers
 # ---------------------------------------------------------------------------
 def partition_by_owner(keys, world, n_dev=None):

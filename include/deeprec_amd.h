@@ -1929,6 +1929,44 @@ int dr_co_action_backward(const float* param, int64_t ld_param, const float* his
                           int order_indep, float* grad_his, float* grad_param, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* FiBiNET's bilinear interaction (Huang et al., RecSys 2019) over every     */
+/* pair of fields, fp32 on the matrix cores (csrc/bilinear.hip).  */
+/* With v = x, or v[b, i, :] = scale[b, i] x[b, i, :] (SENET's weights,      */
+/* applied on the way in; scale NULL: none):                                 */
+/*   out[b, p(i, j), d] = (sum_k v[b, i, k] W[sel, k, d]) v[b, j, d]   i < j */
+/* p(i, j) is the row-major upper-triangle index (itertools.combinations'    */
+/* order), P = m (m - 1) / 2 pairs; kind 0 (field-all): sel = 0, weight [1,  */
+/* D, D]; 1 (field-each): sel = i, weight [m, D, D] (the last matrix is      */
+/* never used); 2 (field-interaction): sel = p, weight [P, D, D].  x [B, m,  */
+/* D], scale [B, m], out [B, P, D]; all contiguous.  B >= 1, 2 <= m <= 64,   */
+/* 1 <= D <= 64; anything else is DR_INVALID_ARGUMENT before any launch.     */
+/* Nothing is saved by the forward.  No allocation, host read,               */
+/* synchronisation or atomics; every launch captures into a graph.  A        */
+/* sample's out, grad_x and grad_scale are bitwise independent of B and of   */
+/* its neighbours; grad_weight is a sum over the batch in an order fixed by  */
+/* (kind, B, m, D): identical from run to run.                               */
+/* ------------------------------------------------------------------------ */
+/* 0 for shapes outside the native set; 64 MiB at the most.                  */
+size_t dr_bilinear_workspace_size(int kind, int64_t batch, int64_t fields, int64_t width);
+int dr_bilinear_forward(const float* x, const float* scale /* nullable */, const float* weight,
+                        int kind, int64_t batch, int64_t fields, int64_t width, float* out,
+                        void* stream);
+/* Backward from grad_out [B, P, D], recomputing u = v W:                    */
+/*   gv[b, j, :] += grad_out[b, p, :] * u        gu = grad_out[b, p, :] * v[b, j, :] */
+/*   gv[b, i, :] += gu W[sel]^T                  grad_weight[sel] += v[b, i, :]^T gu */
+/*   grad_x = scale gv      grad_scale[b, i] = sum_d gv[b, i, d] x[b, i, d]  */
+/* grad_x [B, m, D], grad_scale [B, m] (NULL when scale is NULL, or not      */
+/* wanted) and grad_weight (weight's shape) are written in full.  workspace: */
+/* dr_bilinear_workspace_size bytes (the weight gradient's per-slice         */
+/* partials).  One launch for grad_x and grad_scale, one and a finishing     */
+/* launch for grad_weight.                                                   */
+int dr_bilinear_backward(const float* x, const float* scale /* nullable */, const float* weight,
+                         const float* grad_out, int kind, int64_t batch, int64_t fields,
+                         int64_t width, float* grad_x, float* grad_scale /* nullable */,
+                         float* grad_weight, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* String -> id, the step before the lookup. Strings are one byte buffer    */
 /* plus int64 offsets[n+1] (string i = bytes[offsets[i] .. offsets[i+1])).   */
 /* ------------------------------------------------------------------------ */

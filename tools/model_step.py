@@ -19,7 +19,7 @@ Prints one JSON
 line with samples/s and the per-phase split.  A measurement aid for
 SURVEY 8f #4; bench.py's headline metric is the forward lookup.
 
-  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|can|mmoe|ple|masknet|xdeepfm|dcn|wdl] [--rows 12500000] [--dim 128]
+  python tools/model_step.py [--model dlrm|deepfm|din|dien|bst|can|mmoe|ple|masknet|xdeepfm|fibinet|dcn|wdl] [--rows 12500000] [--dim 128]
 """
 import argparse
 import json
@@ -37,12 +37,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dlrm",
                     choices=["dlrm", "deepfm", "din", "dien", "bst", "can", "mmoe", "ple", "masknet",
-                             "xdeepfm", "dcn", "wdl"])
+                             "xdeepfm", "fibinet", "dcn", "wdl"])
+    ap.add_argument("--kind", default="interaction", choices=["all", "each", "interaction"],
+                    help="FiBiNET: the bilinear layer's weight sharing")
     ap.add_argument("--parallel", action="store_true", help="MaskNet: the parallel model")
     ap.add_argument("--maxlen", type=int, default=100, help="DIN history length bound")
     ap.add_argument("--tables", type=int, default=26)
     ap.add_argument("--rows", type=int, default=12_500_000)
-    ap.add_argument("--dim", type=int, default=None, help="128 (MaskNet, xDeepFM: 16)")
+    ap.add_argument("--dim", type=int, default=None, help="128 (MaskNet, xDeepFM, FiBiNET: 16)")
     ap.add_argument("--batch", type=int, default=None, help="65536 (DIN: 4096)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -60,7 +62,7 @@ def main():
         args.batch = args.batch or 65536
         return wdl(args, dr, mz, dev)
     args.batch = args.batch or 65536
-    args.dim = args.dim or (16 if args.model in ("masknet", "xdeepfm") else 128)
+    args.dim = args.dim or (16 if args.model in ("masknet", "xdeepfm", "fibinet") else 128)
     T, D, B, R = args.tables, args.dim, args.batch, args.rows
     t0 = time.perf_counter()
     evs = []
@@ -78,6 +80,8 @@ def main():
                            bf16=args.bf16).to(dev)
     elif args.model == "xdeepfm":
         model = mz.XDeepFM(evs, 13).to(dev)
+    elif args.model == "fibinet":
+        model = mz.FiBiNET(evs, 13, kind=args.kind).to(dev)
     elif args.model == "dcn":     # BASELINE configs[4]: bf16 CrossNet on MFMA, 3 layers
         model = mz.DCNv2(evs, 13, layers=3, deep=(1024, 512), bf16=args.bf16).to(dev)
     else:
@@ -122,6 +126,8 @@ def main():
         res["mode"], res["layer_norm"] = model.mode, os.environ.get("DR_LAYER_NORM", "native")
     if args.model == "xdeepfm":
         res["cin"] = os.environ.get("DR_CIN", "native")
+    if args.model == "fibinet":
+        res["kind"], res["bilinear"] = args.kind, os.environ.get("DR_BILINEAR", "native")
     print(json.dumps(res), flush=True)
 
 
